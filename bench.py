@@ -19,13 +19,19 @@ one camera, the reference's --input-dir path), so a rank renders its block with 
 kernel launch per 16 frames (lrp_reproject_batch_device); `--per-frame-launches`
 issues one launch per frame instead, round-robin over `--streams` HIP streams.
 
-Reported next to the headline value, all measured in this process:
-  roofline            dominant kernel of the headline workload, HIP events on its stream
-                      (frac = read + write algorithmic bytes / time / 8 TB/s,
-                       frac_read_only = source bytes only, single_launch_us = one frame per launch)
-  secondary           the same figures for north_star's target case (equirect -> rect bicubic)
+A plain run sets up, warms up, times the steps and prints the line; next to the headline value
+(and ms_per_step, the wall time of one timed step) it reports
+  roofline            dominant kernel of the headline workload, from the HIP events around the
+                      launches of the timed region (frac = read + write algorithmic bytes / time / 8 TB/s,
+                      frac_read_only = source bytes only)
+`--dump-outputs DIR` writes a seeded sample of what the last timed step rendered (dump_outputs).
+`--full` measures and checks the rest, all in this process:
+  roofline            + single_launch_us = one frame per launch (and two-stream / uncached variants)
+  secondary           the same figures for the other workloads of DEFAULT_SECONDARY
   outputs_digest      sha256 over the per-image 64-bit checksums of the rendered batch, in
-                      image order: equal for any N (tests/test_bench_multi_rank.py)
+                      image order: equal for any N (tests/test_bench_multi_rank.py), and
+                      compared with the oracle's committed checksums (exit status 3 if they differ)
+  staged              host-buffer (PCIe-inclusive) rates, tools/staged_bench
   cpu_baseline        the oracle on this host's cores, one image per thread
 """
 import argparse
@@ -285,7 +291,7 @@ def parse_args():
     ap.add_argument("--workload", default="fisheye_to_rect_bicubic", choices=sorted(WORKLOADS))
     ap.add_argument("--secondary", default=None,
                     help="comma-separated workloads measured (kernel timing only) in the same process; '' = none "
-                         "(default: the seven of DEFAULT_SECONDARY at N = 1, none at N > 1)")
+                         "(default: those of DEFAULT_SECONDARY with --full at N = 1, none otherwise)")
     ap.add_argument("--size", type=int, default=0, help="override the frame size (tests; 0 = the workload's 4096)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of the barrier / max-time reduction for --gpus > 1 (nccl = RCCL; "
@@ -297,9 +303,19 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-staged", action="store_true", help="skip the host-buffer (PCIe-inclusive) leg (tools/staged_bench)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--detail-file", default="bench_detail.json",
+    ap.add_argument("--detail-file", default=None,
                     help="rank 0 writes the full result here (notes, traffic detail, two-stream / uncached single launches, per-rank "
-                         "times, staged rates); stdout carries the compact line only.  '' = do not write")
+                         "times, staged rates); stdout carries the compact line only.  '' = do not write (default: "
+                         "bench_detail.json with --full, none otherwise)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure as well: the single-launch / two-stream / "
+                         "uncached legs, the secondary workloads, the host-buffer leg, the CPU baseline, the per-image checksums "
+                         "against the committed oracle fixture and the detail file (default: set up, warm up, time the steps, "
+                         "print the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last step rendered as DIR/<name>.npy: a fixed, seeded "
+                         "sample of pixels of every image of the batch and a full-resolution crop of image 0 (float32), and the "
+                         "sampled positions (float64); < 64 MB in all")
     ap.add_argument("--force-dist", action="store_true",
                     help="--gpus 1 through the N > 1 code path: started under torch.distributed.run with one rank, process group "
                          "initialised (nccl = RCCL), barriers and the device-side MAX reduction run on a world-size-1 communicator — "
@@ -510,6 +526,41 @@ def golden_batch_digest(workload, total_images):
     return hashlib.sha256(",".join(sums[:total_images]).encode()).hexdigest()
 
 
+DUMP_SAMPLE_BYTES = 48 << 20  # the per-image pixel samples; the crop of image 0 adds at most 256^2 pixels
+DUMP_CROP = 256
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(torch, dsts, n_images, total_images, dist, rank, out_dir):
+    """What the last timed step rendered, as .npy files in `out_dir` (rank 0 writes; float32): the same seeded sample of pixel
+    positions of every image of the batch, in image order over all ranks (outputs_sample: images x pixels x channels; image k of
+    a rank's block is in resident destination k % len(dsts)), the sampled positions (pixel_index, row-major, float64) and the
+    central DUMP_CROP^2 window of image 0 at full resolution (image0_crop).  A frame's output is 256 MiB: the sample keeps a run
+    under 64 MB whatever the batch."""
+    import numpy as np
+
+    h, w, c = dsts[0].shape
+    per_image = max(1, min(h * w, DUMP_SAMPLE_BYTES // (total_images * c * 4)))
+    rng = np.random.default_rng(DUMP_SEED)
+    pix = np.arange(h * w) if per_image == h * w else np.sort(rng.choice(h * w, per_image, replace=False))
+    idx = torch.from_numpy(pix).to(dsts[0].device)
+    slots = [d.view(-1, c).index_select(0, idx).cpu().numpy() for d in dsts[:n_images]]
+    sample = np.stack([slots[k % len(slots)] for k in range(n_images)]) if n_images else np.empty((0, per_image, c), np.float32)
+    blocks = [sample]
+    if dist is not None:
+        blocks = [None] * dist.get_world_size()
+        dist.all_gather_object(blocks, sample)
+    if rank != 0:
+        return
+    ch, cw = min(DUMP_CROP, h), min(DUMP_CROP, w)
+    y0, x0 = (h - ch) // 2, (w - cw) // 2
+    crop = dsts[0][y0:y0 + ch, x0:x0 + cw].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "outputs_sample.npy"), np.concatenate(blocks).astype(np.float32, copy=False))
+    np.save(os.path.join(out_dir, "pixel_index.npy"), pix.astype(np.float64))
+    np.save(os.path.join(out_dir, "image0_crop.npy"), crop.astype(np.float32, copy=False))
+
+
 # ---- the line the driver reads --------------------------------------------------------------------------------------
 # bench.py's LAST stdout line is ONE compact JSON object (the contract keys + the roofline and cpu_baseline objects + one
 # {frac, us_per_frame} pair per secondary workload); everything else that is measured — notes, traffic detail, two-stream and
@@ -683,15 +734,18 @@ def main():
     elapsed = sharding.max_over_ranks(elapsed_rank, dist, dev if args.dist_backend == "nccl" else None, always=args.force_dist)
     # full 16-frame launches of the timed region (a shard's last launch may hold fewer frames)
     timed_ms = [a.elapsed_time(b) for per_step in events for (a, b), g in zip(per_step, groups) if g._n == FRAMES_PER_LAUNCH]
+    if args.dump_outputs:  # (before anything else renders into the destinations)
+        dump_outputs(torch, dsts, len(shard), total_images, dist, rank, args.dump_outputs)
 
-    # per-image checksums of what the timed steps rendered (only when every image of the shard has its
+    # --full: per-image checksums of what the timed steps rendered (only when every image of the shard has its
     # own resident destination), gathered in image order — a reporting step, not on the data path
-    sums = pkg.checksums(dsts[: len(shard)]) if shard and n_res >= len(shard) else None
-    all_sums = [sums]
-    if dist is not None:
-        all_sums = [None] * world
-        dist.all_gather_object(all_sums, sums)
-    digest = None
+    all_sums, digest = [None], None
+    if args.full or args.checksums_file:
+        sums = pkg.checksums(dsts[: len(shard)]) if shard and n_res >= len(shard) else None
+        all_sums = [sums]
+        if dist is not None:
+            all_sums = [None] * world
+            dist.all_gather_object(all_sums, sums)
     if all(s is not None for s in all_sums):
         flat = [v for s in all_sums for v in s]
         digest = hashlib.sha256(",".join(f"{v:016x}" for v in flat).encode()).hexdigest()
@@ -700,15 +754,21 @@ def main():
                 json.dump({"images": total_images, "n_gpus": world, "checksums": [f"{v:016x}" for v in flat]}, f)
 
     bad_pixels = False
-    # N > 1: rank 0 reports the timed region only and the other ranks are released at once (the single-launch legs and the
-    # secondary workloads are N = 1 measurements: ~15 s during which seven GPUs would sit in a barrier); --full-legs overrides.
-    full_legs = world == 1 or args.full_legs
+    # Without --full a run reports the timed region only.  N > 1: rank 0 reports the timed region only and the other ranks are
+    # released at once (the single-launch legs and the secondary workloads are N = 1 measurements: ~15 s during which seven GPUs
+    # would sit in a barrier); --full-legs overrides.
+    full_legs = (world == 1 and args.full) or args.full_legs
     if args.secondary is None:
         args.secondary = DEFAULT_SECONDARY if full_legs else ""
+    if args.detail_file is None:
+        args.detail_file = "bench_detail.json" if args.full else ""
     if rank == 0:
         res = min(n_res, 64)
+        # the headline kernel's figures come from the launches of the timed region; only --full times launches of its own
+        # when the region holds fewer than four full 16-frame launches
+        region_ms = timed_ms if len(timed_ms) >= 4 or (timed_ms and not args.full) else None
         roof = kernel_figures(torch, pkg, wl, size, srcs[:res], [[d] for d in dsts[:res]], streams[0], args.workload,
-                              timed_region_ms=timed_ms if len(timed_ms) >= 4 else None, single_legs=full_legs)
+                              timed_region_ms=region_ms, single_legs=full_legs) if region_ms or args.full else None
         # (the un-fused IEEE arithmetic of the reference makes this kernel VALU-bound, not HBM-bound — DESIGN.md section 5;
         # frac is algorithmic bytes / kernel time / 8 TB/s as the contract asks)
         secondary = {}
@@ -724,7 +784,8 @@ def main():
                 del s2, d2
                 torch.cuda.empty_cache()
         value = total_images * size * size * args.steps / elapsed / 1e6
-        golden = golden_batch_digest(args.workload, total_images) if size == wl["size"] and args.scaling == "strong" else None
+        golden = (golden_batch_digest(args.workload, total_images) if args.full and size == wl["size"] and args.scaling == "strong"
+                  else None)
         out = {
             "metric": f"Mpix/s reprojected ({'4K' if size == 4096 else size} {'RGBA' if c == 4 else f'{c}-channel'} float, "
                       f"{INTERP_NAMES[wl['interp']]})",
@@ -764,9 +825,9 @@ def main():
             "roofline": roof,
             "secondary": secondary,
         }
-        if world == 1 and not args.no_staged:
+        if world == 1 and args.full and not args.no_staged:
             out["staged"] = staged_rates()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pkg, wl, args.cpu_seconds)
         detail_file = None
         if args.detail_file:

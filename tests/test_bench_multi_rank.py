@@ -40,7 +40,7 @@ def run_bench(n, tmp_path, extra=(), backend="gloo"):
     """-> (the detail record bench.py wrote, the per-image checksums); the compact line is checked on the way."""
     out = tmp_path / f"sums_{n}.json"
     detail = tmp_path / f"detail_{n}.json"
-    args = ["--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", str(BATCH), "--size", str(SIZE),
+    args = ["--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", str(BATCH), "--size", str(SIZE), "--full",
             "--no-cpu-baseline", "--secondary", "", "--settle-seconds", "0", "--dist-backend", backend, "--checksums-file", str(out),
             "--detail-file", str(detail), *extra]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")

@@ -9,7 +9,7 @@ out=gpurun_out/final; rm -rf $out gpurun_out/traffic; mkdir -p $out
 # the PMC traffic first: bench.py reports roofline.traffic only from a file stamped with the sources it runs
 bash tools/collect_traffic.sh $round > $out/traffic.log 2>&1; tail -2 $out/traffic.log; cp gpurun_out/traffic_$round.json profiles/traffic_$round.json
 # bench.json = the detail file (everything measured); bench_line.json = the compact line the driver reads (stdout)
-(timeout 1200 python bench.py --detail-file $out/bench.json > $out/bench_line.json 2> $out/bench.err; echo "bench rc=$?"; tail -c 4200 $out/bench_line.json)
+(timeout 1200 python bench.py --full --detail-file $out/bench.json > $out/bench_line.json 2> $out/bench.err; echo "bench rc=$?"; tail -c 4200 $out/bench_line.json)
 ALL="eqd_rect_bc eqr_rect_bc eqr_rect_bc_rot eqr_rect_bc_pitch eqr_rect_bc_gen rect_rect_bc eqd_eqd_bc eqr_eqr_bc_rot eqr_eqd_bc_rot rect_eqd_bc rect_eqr_bc eqr_eqd_bl_rot eqr_rect_bl eqr_rect_nn eqr_rect_bl_rot eqr_rect_nn_rot"
 BC="eqd_rect_bc eqr_rect_bc eqr_rect_bc_rot eqr_rect_bc_pitch eqr_rect_bc_gen rect_rect_bc eqr_eqd_bc_rot rect_eqr_bc"
 timeout 300 ./tools/kbench --sum --reps 32 --distinct 16 $ALL > $out/kbench_rgba_single.log 2>&1
@@ -61,7 +61,7 @@ timeout 300 ./tools/staged_bench > $out/staged.log 2>&1
 (echo "# RGBA"; python3 tools/fov_sweep.py 4 2>&1 | grep focal; echo "# RGBAZ + tonemap"; python3 tools/fov_sweep.py 5 post 2>&1 | grep focal) > $out/fov_sweep.log
 timeout 100 tools/microbench/hbm_stream > $out/hbm_stream.log 2>&1
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof_bench -- python3 $R/bench.py --no-cpu-baseline --no-staged --detail-file "" > $R/$out/prof_bench.log 2>&1; echo "rocprof rc=$?"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof_bench -- python3 $R/bench.py --full --no-cpu-baseline --no-staged --detail-file "" > $R/$out/prof_bench.log 2>&1; echo "rocprof rc=$?"
 cat $R/$out/prof_bench/*/*kernel_stats.csv | cut -c1-200
 python3 $R/tools/kernel_trace_summary.py $(ls -t $R/$out/prof_bench/*/*kernel_trace.csv | head -1) | tee $R/$out/kernel_trace_by_launch_shape.txt
 i=0
