@@ -14,6 +14,7 @@
 #include <filesystem>
 #include <stdexcept>
 
+#include "lrp.h"
 #include "lrp_cli_options.h"
 #include "lrp_engine.h"
 #include "lrp_run_plan.h"
@@ -31,6 +32,7 @@ int main(int argc, char **argv) {
     std::printf("%s\n", help_text(argv[0]).c_str());
     return 0;
   }
+  if (cl.has("allow-equisolid")) lrp_lens_extensions(LRP_LENS_EXT_EQUISOLID); // the opt-in lens extension (include/lrp.h)
   RunPlan plan;
   if (int rc = resolve_run_plan(cl, argv[0], plan)) return rc;
 

@@ -105,6 +105,14 @@ class LensInfo:
         return cls._from_c(c)
 
     @classmethod
+    def equisolid(cls, focal_length, sensor_width, fov, res_x, res_y):
+        """--equisolid focal_len,sensor_width,fov (src/main.cpp:31-46): sensor_height = res_y / res_x * sensor_width.
+        Renders only while the LENS_EXT_EQUISOLID extension is on (lens_extensions)."""
+        c = LrpLens()
+        _native.load().lrp_lens_equisolid(ctypes.byref(c), focal_length, sensor_width, fov, res_x, res_y)
+        return cls._from_c(c)
+
+    @classmethod
     def equirectangular(cls, longitude_min=None, longitude_max=None, latitude_min=None, latitude_max=None):
         """--equirectangular full | lon_min,lon_max,lat_min,lat_max (src/main.cpp:58-95)."""
         c = LrpLens()
@@ -204,6 +212,15 @@ def debug_kernel(choice=-1):
     bicubic, 3 the same without shared tap coefficients; all produce the same bits);
     returns the previous choice.  -1 only queries."""
     return _native.load().lrp_debug_kernel(int(choice))
+
+
+LENS_EXT_EQUISOLID = 1  # include/lrp.h LRP_LENS_EXT_EQUISOLID
+
+
+def lens_extensions(mask=None):
+    """lrp_lens_extensions: the process-wide mask of opt-in lens extensions (0 by default: the reference's lenses only).
+    Sets it and returns the previous mask; None only queries."""
+    return _native.load().lrp_lens_extensions(-1 if mask is None else int(mask))
 
 
 def debug_set(name, value=-1):

@@ -153,6 +153,11 @@ SYMBOLS = {
         [_P(LrpLens), ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float],
     ),
     "lrp_lens_equidistant": (None, [_P(LrpLens), ctypes.c_float]),
+    "lrp_lens_equisolid": (
+        None,
+        [_P(LrpLens), ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float],
+    ),
+    "lrp_lens_extensions": (ctypes.c_int, [ctypes.c_int]),
     "lrp_lens_equirectangular": (
         None,
         [_P(LrpLens), ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float],

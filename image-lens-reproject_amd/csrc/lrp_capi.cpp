@@ -20,12 +20,14 @@
 #include <vector>
 
 #include "../../include/lrp.h"
+#include "lrp_eqs.h"
 #include "lrp_geocache.h"
 #include "lrp_params.h"
 #include "lrp_plan.h"
 #include "lrp_tables.h"
 
 namespace lrp {
+EqsLaunchers g_eqs_launchers = {}; // (lrp_eqs.h: filled in by the units of the equisolid kernels when the library loads)
 hipError_t launch_nearest(const KParams &P, int out_idx, int in_mode, hipStream_t stream);
 hipError_t launch_bilinear(const KParams &P, int out_idx, int in_mode, hipStream_t stream);
 hipError_t launch_bicubic(const KParams &P, int out_idx, int in_mode, hipStream_t stream);
@@ -89,11 +91,20 @@ int select_device(int device) {
   return LRP_OK;
 }
 
-bool lens_in_hot_path(int type) {
-  return type == LRP_RECTILINEAR || type == LRP_FISHEYE_EQUIDISTANT || type == LRP_EQUIRECTANGULAR;
+// Opt-in lens extensions (lrp_lens_extensions): a mask of LRP_LENS_EXT_*, 0 — the reference's lenses only — by default.
+std::atomic<int> g_lens_ext{0};
+
+// `ext`: the extension mask, read once per call
+bool lens_in_hot_path(int type, int ext) {
+  return type == LRP_RECTILINEAR || type == LRP_FISHEYE_EQUIDISTANT || type == LRP_EQUIRECTANGULAR ||
+         (type == LRP_FISHEYE_EQUISOLID && (ext & LRP_LENS_EXT_EQUISOLID) != 0);
 }
 
-int out_lens_index(int type) { return type == LRP_RECTILINEAR ? 0 : (type == LRP_FISHEYE_EQUIDISTANT ? 1 : 2); }
+// out_idx of the existing kernel tables: 0 rectilinear, 1 equidistant (and the equisolid lens where a table of the radial
+// target stands in for it: the launches that read the geometry cache hold no lens math), 2 equirectangular
+int out_lens_index(int type) { return type == LRP_RECTILINEAR ? 0 : ((type == LRP_FISHEYE_EQUIDISTANT || type == LRP_FISHEYE_EQUISOLID) ? 1 : 2); }
+// the lens ids of lrp_params.h (kRect / kEquidistant / kEquisolid / kEquirect: the numbering of include/lrp.h)
+int out_lens_id(int type) { return type; }
 
 // LoopHorizontally decision, reference src/reproject.cpp:386-394: float span,
 // compared in double against 2*M_PI with a float threshold.
@@ -105,6 +116,7 @@ bool source_wraps(const lrp_lens &L) {
 int in_lens_mode(const lrp_lens &L) {
   if (L.type == LRP_RECTILINEAR) return lrp::kInRect;
   if (L.type == LRP_FISHEYE_EQUIDISTANT) return lrp::kInEquidistant;
+  if (L.type == LRP_FISHEYE_EQUISOLID) return lrp::kInEquisolid;
   return source_wraps(L) ? lrp::kInEquirectLoop : lrp::kInEquirect;
 }
 
@@ -132,8 +144,9 @@ bool image_fits_byte_offsets(const lrp_image &im) { return (unsigned long long)i
 // then the preconditions the reference leaves unchecked.
 int validate(const lrp_image *in, const lrp_image *out, int interpolation, bool need_data) {
   if (!in || !out) return fail(LRP_ERR_NULL, "null image");
-  if (!lens_in_hot_path(out->lens.type)) return fail(LRP_ERR_OUTPUT_LENS, "Output lens type not supported.");
-  if (!lens_in_hot_path(in->lens.type)) return fail(LRP_ERR_INPUT_LENS, "Input lens type not supported.");
+  const int ext = g_lens_ext.load(std::memory_order_relaxed);
+  if (!lens_in_hot_path(out->lens.type, ext)) return fail(LRP_ERR_OUTPUT_LENS, "Output lens type not supported.");
+  if (!lens_in_hot_path(in->lens.type, ext)) return fail(LRP_ERR_INPUT_LENS, "Input lens type not supported.");
   if (interpolation != LRP_NEAREST && interpolation != LRP_BILINEAR && interpolation != LRP_BICUBIC)
     return fail(LRP_ERR_INTERPOLATION, "Interpolation method not supported.");
   if (in->channels < 1 || in->channels != out->channels)
@@ -175,6 +188,9 @@ lrp::KParams make_params(const lrp_image *in, const lrp_image *out, int num_samp
   // reference performs per pixel (src/reproject.cpp:178,196,265-266)
   P.in_focal = in->lens.sensor_width / in->lens.u.fisheye_equidistant.fov;
   P.out_focal = out->lens.sensor_width / out->lens.u.fisheye_equidistant.fov;
+  // equisolid: 2.0f * focal_length, exact (r = 2 f sin(theta / 2), include/lrp.h)
+  if (in->lens.type == LRP_FISHEYE_EQUISOLID) P.in_focal = 2.0f * in->lens.u.fisheye_equisolid.focal_length;
+  if (out->lens.type == LRP_FISHEYE_EQUISOLID) P.out_focal = 2.0f * out->lens.u.fisheye_equisolid.focal_length;
   P.in_lon_span = in->lens.u.equirectangular.longitude_max - in->lens.u.equirectangular.longitude_min;
   P.in_lat_span = in->lens.u.equirectangular.latitude_max - in->lens.u.equirectangular.latitude_min;
   return P;
@@ -290,8 +306,8 @@ lrp::PlanSwitches plan_switches() {
 lrp::PlanRequest plan_request(const lrp_image *in, const lrp_image *out, int num_samples, int interpolation, const float *rotation,
                               int n_batch, bool band) {
   lrp::PlanRequest r;
-  r.out_type = out->lens.type == LRP_RECTILINEAR ? lrp::kPlanRect : (out->lens.type == LRP_FISHEYE_EQUIDISTANT ? lrp::kPlanEquidistant : lrp::kPlanEquirect);
-  r.in_type = in->lens.type == LRP_RECTILINEAR ? lrp::kPlanRect : (in->lens.type == LRP_FISHEYE_EQUIDISTANT ? lrp::kPlanEquidistant : lrp::kPlanEquirect);
+  r.out_type = out_lens_id(out->lens.type);
+  r.in_type = out_lens_id(in->lens.type);
   r.in_mode = in_lens_mode(in->lens);
   r.out_w = out->width, r.out_h = out->height, r.in_w = in->width, r.in_h = in->height, r.channels = out->channels;
   r.num_samples = num_samples, r.interpolation = interpolation;
@@ -303,10 +319,15 @@ lrp::PlanRequest plan_request(const lrp_image *in, const lrp_image *out, int num
   r.byte_offsets_fit = image_fits_byte_offsets(*in) && image_fits_byte_offsets(*out);
   return r;
 }
-static_assert((int)lrp::kPlanRect == (int)lrp::kRect && (int)lrp::kPlanEquidistant == (int)lrp::kEquidistant && (int)lrp::kPlanEquirect == (int)lrp::kEquirect,
+static_assert((int)lrp::kPlanRect == (int)lrp::kRect && (int)lrp::kPlanEquidistant == (int)lrp::kEquidistant && (int)lrp::kPlanEquirect == (int)lrp::kEquirect &&
+                  (int)lrp::kPlanEquisolid == (int)lrp::kEquisolid,
               "lrp_plan.h numbers lenses like lrp_params.h");
+static_assert((int)lrp::kRect == LRP_RECTILINEAR && (int)lrp::kEquidistant == LRP_FISHEYE_EQUIDISTANT && (int)lrp::kEquisolid == LRP_FISHEYE_EQUISOLID &&
+                  (int)lrp::kEquirect == LRP_EQUIRECTANGULAR,
+              "lrp_params.h numbers lenses like include/lrp.h (out_lens_id)");
 static_assert((int)lrp::kPlanInRect == (int)lrp::kInRect && (int)lrp::kPlanInEquidistant == (int)lrp::kInEquidistant &&
-                  (int)lrp::kPlanInEquirect == (int)lrp::kInEquirect && (int)lrp::kPlanInEquirectLoop == (int)lrp::kInEquirectLoop,
+                  (int)lrp::kPlanInEquirect == (int)lrp::kInEquirect && (int)lrp::kPlanInEquirectLoop == (int)lrp::kInEquirectLoop &&
+                  (int)lrp::kPlanInEquisolid == (int)lrp::kInEquisolid,
               "lrp_plan.h numbers input modes like lrp_params.h");
 static_assert((int)lrp::kPlanNearest == LRP_NEAREST && (int)lrp::kPlanBilinear == LRP_BILINEAR && (int)lrp::kPlanBicubic == LRP_BICUBIC, "interpolation numbering");
 
@@ -324,6 +345,11 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
   }
   const int oi = out_lens_index(out->lens.type);
   const int im = in_lens_mode(in->lens);
+  // The equisolid lens (either side): its own kernels (lrp_eqs.h) — except where the geometry cache is read: those kernels
+  // hold no lens math, and the clamped, non-wrapping equidistant source's instantiation serves (im_std).
+  const int out_id = out_lens_id(out->lens.type);
+  const bool eqs = lrp::eqs_cell(out_id, im) >= 0;
+  const int im_std = im == lrp::kInEquisolid ? lrp::kInEquidistant : im;
   hipError_t e;
   lrp::TableLease lease; // pins the cached tables until every launch of this call is enqueued (scope end)
   lrp::GeoUse geo;       // this launch's use of the geometry cache (none unless set below)
@@ -370,7 +396,7 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
       lrp::GeoKey key;
       std::memset(&key, 0, sizeof(key));
       key.device = device;
-      key.out_type = oi == 0 ? lrp::kRect : (oi == 1 ? lrp::kEquidistant : lrp::kEquirect);
+      key.out_type = out_id;
       key.in_mode = im;
       key.out_w = out->width, key.out_h = out->height, key.in_w = in->width, key.in_h = in->height;
       key.has_rot = P.has_rot;
@@ -414,11 +440,15 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
         }
       }
       if (window && P.geo_mode == 2 && P.big_windows != 0) g_knobs[kKnobBigLaunches].fetch_add(1, std::memory_order_relaxed);
-      if (window) return lrp::launch_win_bicubic(P, oi, im, stream);
-      if (P.geo_mode == 2 && num_samples > 1) return lrp::launch_ss_gather(P, interpolation, im, stream); // (a lane per sub-sample: coalesced loads of the entry)
-      if (interpolation == LRP_NEAREST) return lrp::launch_tile_nearest(P, oi, im, stream);
-      if (interpolation == LRP_BILINEAR) return lrp::launch_tile_bilinear(P, oi, im, stream);
-      return lrp::launch_tile_bicubic(P, oi, im, stream);
+      if (eqs && P.geo_mode != 2) {
+        const lrp::EqsLaunchFn fn = window ? lrp::g_eqs_launchers.win : lrp::g_eqs_launchers.tile[interpolation];
+        return fn ? fn(P, out_id, im, stream) : hipErrorInvalidDeviceFunction;
+      }
+      if (window) return lrp::launch_win_bicubic(P, oi, im_std, stream);
+      if (P.geo_mode == 2 && num_samples > 1) return lrp::launch_ss_gather(P, interpolation, im_std, stream); // (a lane per sub-sample: coalesced loads of the entry)
+      if (interpolation == LRP_NEAREST) return lrp::launch_tile_nearest(P, oi, im_std, stream);
+      if (interpolation == LRP_BILINEAR) return lrp::launch_tile_bilinear(P, oi, im_std, stream);
+      return lrp::launch_tile_bicubic(P, oi, im_std, stream);
     };
     if (n_batch <= 0) {
       e = launch();
@@ -448,7 +478,7 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
       // census of its windows are built behind it, and their header follows the records to the host (page-locked; read once
       // the records' event has completed)
       const uint8_t *const header = reinterpret_cast<const uint8_t *>(geo.box) + lrp::geo_lists_offset(out->width, out->height);
-      const bool with_lists = im == lrp::kInRect && knob(kKnobGeoLists) != 0, with_census = knob(kKnobGeoCensus) != 0 && im != lrp::kInEquidistant;
+      const bool with_lists = im == lrp::kInRect && knob(kKnobGeoLists) != 0, with_census = knob(kKnobGeoCensus) != 0 && im != lrp::kInEquidistant && im != lrp::kInEquisolid;
       if (!with_lists && !with_census) {
         // (nothing to tell the host about this entry)
       } else if ((!with_lists || lrp::launch_geo_build_lists(geo.box, out->width, out->height, P.alias_pairs, stream) == hipSuccess) &&
@@ -472,7 +502,9 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
         P.dst = out[i].data + c0;
         P.ch_count = std::min(group, C - c0);
         P.has_post = post != nullptr && c0 == 0;
-        if (interpolation == LRP_NEAREST)
+        if (eqs)
+          e = lrp::g_eqs_launchers.pixel ? lrp::g_eqs_launchers.pixel(P, interpolation, out_id, im, stream) : hipErrorInvalidDeviceFunction;
+        else if (interpolation == LRP_NEAREST)
           e = lrp::launch_nearest(P, oi, im, stream);
         else if (interpolation == LRP_BILINEAR)
           e = lrp::launch_bilinear(P, oi, im, stream);
@@ -551,6 +583,11 @@ struct lrp_context {
 extern "C" {
 
 int lrp_abi_version(void) { return LRP_ABI_VERSION; }
+
+int lrp_lens_extensions(int mask) {
+  if (mask < 0) return g_lens_ext.load(std::memory_order_relaxed);
+  return g_lens_ext.exchange(mask & LRP_LENS_EXT_EQUISOLID, std::memory_order_relaxed);
+}
 
 int lrp_debug_kernel(int choice) {
   if (choice < 0 || choice > 3) return kernel_choice();

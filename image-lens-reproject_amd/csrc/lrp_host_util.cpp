@@ -48,6 +48,15 @@ void lrp_lens_equidistant(lrp_lens *lens, float fov) {
   lens->sensor_height = 36.0f;
 }
 
+void lrp_lens_equisolid(lrp_lens *lens, float focal_length, float sensor_width, float fov, float res_x, float res_y) {
+  std::memset(lens, 0, sizeof(*lens));
+  lens->type = LRP_FISHEYE_EQUISOLID;
+  lens->u.fisheye_equisolid.focal_length = focal_length;
+  lens->u.fisheye_equisolid.fov = fov;
+  lens->sensor_width = sensor_width;
+  lens->sensor_height = res_y / res_x * sensor_width; // the CLI's convention, src/main.cpp:45
+}
+
 void lrp_lens_equirectangular(lrp_lens *lens, float longitude_min, float longitude_max, float latitude_min,
                               float latitude_max) {
   std::memset(lens, 0, sizeof(*lens));

@@ -106,7 +106,7 @@ template <int InMode>
 __device__ __forceinline__ void ray_to_source_v2(const KParams &P, float x, float y, float z, float &cx, float &cy) {
   const LensP &L = P.in_lens;
   const float img_w = (float)P.in_w, img_h = (float)P.in_h;
-  if constexpr (InMode == kInRect || InMode == kInEquidistant) {
+  if constexpr (InMode == kInRect || radial_in(InMode)) {
     // x /= -z; y /= -z  (src/reproject.cpp:163-164,191-192).  v / 1.0f == v.
     const float nz = -z;
     if (!wave_all(nz == 1.0f)) {
@@ -125,6 +125,14 @@ __device__ __forceinline__ void ray_to_source_v2(const KParams &P, float x, floa
     const float r_px = r_mm / L.sensor_width * img_w;
     cx = x / r * r_px; // :202-203
     cy = y / r * r_px;
+  } else if constexpr (InMode == kInEquisolid) {
+    // vec_to_equisolid (include/lrp.h): r_mm = 2 f sin(theta / 2), P.in_focal = 2.0f * focal_length (exact)
+    const float r = lrp_sqrtf(x * x + y * y);
+    const float theta = atanf_(r);
+    const float r_mm = P.in_focal * sinf_(0.5f * theta);
+    const float r_px = r_mm / L.sensor_width * img_w;
+    cx = x / r * r_px;
+    cy = y / r * r_px;
   } else {
     const float lat_min = L.p[0], lon_min = L.p[2];
     cx = equirect_cx(x, z, lon_min, P.in_lon_span, img_w);    // :262, :268
@@ -138,6 +146,19 @@ __device__ __forceinline__ void equidistant_ray_v2(const KParams &P, float cx, f
   const float r_px = lrp_sqrtf(cx * cx + cy * cy);
   const float r_mm = r_px / (float)P.out_w * P.out_lens.sensor_width;
   const float theta = r_mm / P.out_focal;
+  float sn, cs;
+  sincosf_(theta, sn, cs);
+  const float s = sn / r_px;
+  vx = s * cx;
+  vy = s * cy;
+  vz = cs;
+}
+
+// equisolid_to_vec (include/lrp.h) with 2.0f * focal_length hoisted into P.out_focal (exact).
+__device__ __forceinline__ void equisolid_ray_v2(const KParams &P, float cx, float cy, float &vx, float &vy, float &vz) {
+  const float r_px = lrp_sqrtf(cx * cx + cy * cy);
+  const float r_mm = r_px / (float)P.out_w * P.out_lens.sensor_width;
+  const float theta = 2.0f * asinf_(r_mm / P.out_focal);
   float sn, cs;
   sincosf_(theta, sn, cs);
   const float s = sn / r_px;
@@ -349,7 +370,7 @@ struct ColTerms {
 template <int OutLens> __device__ __forceinline__ ColTerms column_terms(const KParams &P, int xe, int ssx) {
   const int ns = P.num_samples;
   ColTerms c{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  if constexpr (OutLens != kEquidistant) {
+  if constexpr (!radial_out(OutLens)) {
     if (P.xsep_tab) {
       const int n = P.out_w * ns, j = xe * ns + ssx;
       c.nx = P.xsep_tab[j];
@@ -385,7 +406,10 @@ __device__ __forceinline__ void pixel_ray(const KParams &P, const ColTerms col, 
   } else {
     const float cy = ((float)ye + 0.5f) - (float)P.out_h * 0.5f;                       // :288
     const float scy = cy + ((float)ssy + 1.0f) / ((float)P.num_samples + 1.0f) - 0.5f; // :298
-    equidistant_ray_v2(P, col.a, scy, vx, vy, vz);
+    if constexpr (OutLens == kEquisolid)
+      equisolid_ray_v2(P, col.a, scy, vx, vy, vz);
+    else
+      equidistant_ray_v2(P, col.a, scy, vx, vy, vz);
   }
 }
 
@@ -419,7 +443,7 @@ template <int OutLens, int InMode>
 __device__ __forceinline__ void pixel_plane(const KParams &P, const ColTerms col, float row_v, int ye, int ssy,
                                             float &u, float &v) {
   float vx, vy, vz;
-  if constexpr (OutLens != kEquidistant && InMode != kInEquidistant) {
+  if constexpr (!radial_out(OutLens) && !radial_in(InMode)) {
     // Column-separable source x: when the ray's x and z do not depend on the output row
     // (no rotation, or one whose [0][1] and [2][1] entries are zero) the source x of a
     // rectilinear / equirectangular source is a function of the column alone and comes
@@ -448,7 +472,7 @@ template <int OutLens, int InMode>
 __device__ __forceinline__ void plane_to_texel(const KParams &P, const ColTerms col, float u, float v, float &sx,
                                                float &sy) {
   bool xsep = false;
-  if constexpr (OutLens != kEquidistant && InMode != kInEquidistant) xsep = P.xsep_tab != nullptr;
+  if constexpr (!radial_out(OutLens) && !radial_in(InMode)) xsep = P.xsep_tab != nullptr;
   sx = xsep ? col.sx : texel_coord(u, (float)P.in_w); // :323
   if constexpr (InMode == kInEquirect || InMode == kInEquirectLoop) {
     if (xsep) v = equirect_cy_of_phi(v, P.in_lens.p[0], P.in_lat_span, (float)P.in_h); // :269
@@ -466,7 +490,7 @@ __device__ __forceinline__ void pixel_source_rt(const KParams &P, const ColTerms
 
 // Row term of output row ye, sub-sample ssy (0 for the equidistant target, which has none).
 template <int OutLens> __device__ __forceinline__ float row_term(const KParams &P, int ye, int ssy) {
-  if constexpr (OutLens == kEquidistant)
+  if constexpr (radial_out(OutLens))
     return 0.0f;
   else
     return P.row_tab[ye * P.num_samples + ssy];

@@ -82,8 +82,15 @@ template <int Interp, int CH> struct KernelTable {
   }
 };
 
-// out_idx: 0 rectilinear, 1 equidistant, 2 equirectangular.
-template <int Interp>
+// The kernel of a launch: from the table above (out_idx: 0 rectilinear, 1 equidistant, 2 equirectangular), or from the
+// table of a unit of its own (Pick, the equisolid lens: lrp_eqs_pixel.hip).  Only the picked table is instantiated.
+template <int Interp> struct KernelTablePick {
+  static KernelFn get(const KParams &P, int out_idx, int in_mode) {
+    return (P.channels == 4) ? KernelTable<Interp, 4>::get(out_idx, in_mode) : KernelTable<Interp, 0>::get(out_idx, in_mode);
+  }
+};
+
+template <int Interp, class Pick = KernelTablePick<Interp>>
 hipError_t launch_interp(KParams P, int out_idx, int in_mode, hipStream_t stream) {
   P.tiles_x = (P.out_w + kTileW - 1) / kTileW;
   const int rows = P.y_end - P.y_offset;
@@ -91,8 +98,8 @@ hipError_t launch_interp(KParams P, int out_idx, int in_mode, hipStream_t stream
   const int n_tiles = P.tiles_x * P.tiles_y;
   if (n_tiles <= 0) return hipSuccess;
   const dim3 grid((unsigned)(kXcds * xcd_rows(P.tiles_y) * P.tiles_x)), block(kThreads);
-  KernelFn fn = (P.channels == 4) ? KernelTable<Interp, 4>::get(out_idx, in_mode)
-                                  : KernelTable<Interp, 0>::get(out_idx, in_mode);
+  KernelFn fn = Pick::get(P, out_idx, in_mode);
+  if (!fn) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, grid, block, 0, stream, P);
   return hipGetLastError();
 }

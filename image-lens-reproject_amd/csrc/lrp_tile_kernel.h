@@ -290,8 +290,36 @@ template <int Interp, int CH, bool Frames> struct TileKernelTable {
   }
 };
 
+// The kernel of a launch (P.frames_per_wave and P.geo_mode set): from the tables above, or — Pick of the equisolid lens,
+// lrp_eqs_tile.h — from the table of a unit of its own.  Only the picked tables are instantiated.  kFrameLoop false: the
+// picker has no frame-loop instantiations, a batch renders a frame per workgroup row (blockIdx.y).
+template <int Interp> struct TileTablePick {
+  static constexpr bool kFrameLoop = true;
+  static TileKernelFn get(const KParams &P, int out_idx, int in_mode) {
+    if (P.geo_mode == 2) { // coordinates from the geometry cache (the host asks for it for single whole-image launches only)
+      if constexpr (Interp != 2) {
+        if (P.quad != 0 || P.num_samples != 1 || P.y_offset != 0 || P.y_end != P.out_h) return nullptr;
+        return P.channels == 4 ? TileGeoKernelTable<Interp, 4>::get(in_mode) : P.channels == 3 ? TileGeoKernelTable<Interp, 3>::get(in_mode) : TileGeoKernelTable<Interp, 5>::get(in_mode);
+      } else {
+        return nullptr;
+      }
+    } else if (P.frames_per_wave > 1) {
+      if constexpr (Interp != 2)
+        return P.channels == 4   ? TileKernelTable<Interp, 4, true>::get(out_idx, in_mode)
+               : P.channels == 3 ? TileKernelTable<Interp, 3, true>::get(out_idx, in_mode)
+                                 : TileKernelTable<Interp, 5, true>::get(out_idx, in_mode);
+      else
+        return nullptr;
+    } else {
+      return P.channels == 4   ? TileKernelTable<Interp, 4, false>::get(out_idx, in_mode)
+             : P.channels == 3 ? TileKernelTable<Interp, 3, false>::get(out_idx, in_mode)
+                               : TileKernelTable<Interp, 5, false>::get(out_idx, in_mode);
+    }
+  }
+};
+
 // P.channels must be 3, 4 or 5.
-template <int Interp> hipError_t launch_tile_interp(KParams P, int out_idx, int in_mode, hipStream_t stream) {
+template <int Interp, class Pick = TileTablePick<Interp>> hipError_t launch_tile_interp(KParams P, int out_idx, int in_mode, hipStream_t stream) {
   constexpr int tile_h = tile_rows<Interp>() * kT2Waves;
   if (P.quad) { // the top-left quadrant only: every pixel also renders its three mirror images
     P.tiles_x = ((P.out_w + 1) / 2 + kT2W - 1) / kT2W;
@@ -313,29 +341,12 @@ template <int Interp> hipError_t launch_tile_interp(KParams P, int out_idx, int 
     int F = (int)std::min<long long>(P.batch_n, std::max<long long>(1, units / 4096));
     if (out_idx == 2 && in_mode == kInRect) F = 1; // (see the window kernel: uneven tiles)
     if (frames_override > 0) F = std::max(1, std::min(P.batch_n, frames_override)); // the caller's override (lrp_debug_set "batch_frames": A/B runs, tests)
+    if (!Pick::kFrameLoop) F = 1;
     P.frames_per_wave = F;
     groups = (P.batch_n + F - 1) / F;
   }
-  TileKernelFn fn;
-  if (P.geo_mode == 2) { // coordinates from the geometry cache (the host asks for it for single whole-image launches only)
-    if constexpr (Interp != 2) {
-      if (P.quad != 0 || P.num_samples != 1 || P.y_offset != 0 || P.y_end != P.out_h) return hipErrorInvalidValue;
-      fn = P.channels == 4 ? TileGeoKernelTable<Interp, 4>::get(in_mode) : P.channels == 3 ? TileGeoKernelTable<Interp, 3>::get(in_mode) : TileGeoKernelTable<Interp, 5>::get(in_mode);
-    } else {
-      return hipErrorInvalidValue;
-    }
-  } else if (P.frames_per_wave > 1) {
-    if constexpr (Interp != 2)
-      fn = P.channels == 4   ? TileKernelTable<Interp, 4, true>::get(out_idx, in_mode)
-           : P.channels == 3 ? TileKernelTable<Interp, 3, true>::get(out_idx, in_mode)
-                             : TileKernelTable<Interp, 5, true>::get(out_idx, in_mode);
-    else
-      return hipErrorInvalidValue;
-  } else {
-    fn = P.channels == 4   ? TileKernelTable<Interp, 4, false>::get(out_idx, in_mode)
-         : P.channels == 3 ? TileKernelTable<Interp, 3, false>::get(out_idx, in_mode)
-                           : TileKernelTable<Interp, 5, false>::get(out_idx, in_mode);
-  }
+  const TileKernelFn fn = Pick::get(P, out_idx, in_mode);
+  if (!fn) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3((unsigned)(kXcds * xcd_rows(P.tiles_y) * P.tiles_x), (unsigned)groups), dim3(kT2Threads), 0, stream, P);
   return hipGetLastError();
 }

@@ -1537,7 +1537,24 @@ template <int CH> struct WinSSGeoKernelTable {
 // num_samples must be 1 — or 2, 3, 4 for the SS launcher (a lane per sub-sample).
 // QMode != 0: P.win_mode == QMode, set by the host only for cells where the mode exists.  GeoRead: P.geo_mode == 2, a single
 // whole-image launch.
-template <int QMode, int CH, bool GeoRead = false, bool SS = false>
+// The kernel of a launch (P.frames_per_wave set): from the tables above, or — Pick of the equisolid lens, lrp_eqs_win.h —
+// from the table of a unit of its own.  Only the picked table is instantiated.  kFrameLoop false: the picker has no
+// frame-loop instantiations, a batch renders a frame per workgroup row (blockIdx.y).
+template <int QMode, int CH, bool GeoRead, bool SS> struct WinTablePick {
+  static constexpr bool kFrameLoop = true;
+  static TileKernelFn get(const KParams &P, int out_idx, int in_mode) {
+    if constexpr (SS && GeoRead)
+      return WinSSGeoKernelTable<CH>::get(in_mode);
+    else if constexpr (SS)
+      return WinSSKernelTable<CH>::get(out_idx, in_mode);
+    else if constexpr (GeoRead)
+      return P.frames_per_wave > 1 ? WinGeoFramesKernelTable<CH>::get(in_mode) : WinGeoKernelTable<CH>::get(in_mode, P.big_windows != 0);
+    else
+      return P.frames_per_wave > 1 ? WinKernelTable<QMode, CH, true>::get(out_idx, in_mode) : WinKernelTable<QMode, CH, false>::get(out_idx, in_mode);
+  }
+};
+
+template <int QMode, int CH, bool GeoRead = false, bool SS = false, class Pick = WinTablePick<QMode, CH, GeoRead, SS>>
 inline hipError_t launch_win_bicubic_impl(KParams P, int out_idx, int in_mode, hipStream_t stream) {
   static_assert(!GeoRead || QMode == 0, "the geometry cache feeds plain blocks");
   static_assert(!SS || QMode == 0, "supersampling: plain blocks");
@@ -1595,19 +1612,11 @@ inline hipError_t launch_win_bicubic_impl(KParams P, int out_idx, int in_mode, h
     if (GeoRead && P.big_windows != 0) F = 1; // (the big-window variant has no frame loop: a wavefront per block and frame)
     if (frames_override > 0) F = std::max(1, std::min(P.batch_n, frames_override)); // the caller's override (lrp_debug_set "batch_frames": A/B runs, tests)
     if (P.geo_mode == 1 || P.geo_mode == 3) F = 1; // the launch that writes a geometry-cache entry: the instantiations without the frame loop have the side output
-    if (SS) F = 1;
+    if (SS || !Pick::kFrameLoop) F = 1;
     P.frames_per_wave = F;
     groups = (P.batch_n + F - 1) / F;
   }
-  TileKernelFn fn;
-  if constexpr (SS && GeoRead)
-    fn = WinSSGeoKernelTable<CH>::get(in_mode);
-  else if constexpr (SS)
-    fn = WinSSKernelTable<CH>::get(out_idx, in_mode);
-  else if constexpr (GeoRead)
-    fn = P.frames_per_wave > 1 ? WinGeoFramesKernelTable<CH>::get(in_mode) : WinGeoKernelTable<CH>::get(in_mode, P.big_windows != 0);
-  else
-    fn = P.frames_per_wave > 1 ? WinKernelTable<QMode, CH, true>::get(out_idx, in_mode) : WinKernelTable<QMode, CH, false>::get(out_idx, in_mode);
+  const TileKernelFn fn = Pick::get(P, out_idx, in_mode);
   if (!fn) return hipErrorInvalidValue; // (the host never asks for a mode outside its cells)
   unsigned grid_x = (unsigned)(kXcds * xcd_rows(P.tiles_y, kWinXcdBand) * P.tiles_x);
   if (GeoRead && P.geo_work != nullptr) {

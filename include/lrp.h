@@ -37,10 +37,26 @@ extern "C" {
 typedef enum lrp_lens_type {
   LRP_RECTILINEAR = 0,
   LRP_FISHEYE_EQUIDISTANT = 1,
-  LRP_FISHEYE_EQUISOLID = 2,     /* declared by the reference, rejected by reproject() */
+  LRP_FISHEYE_EQUISOLID = 2,     /* declared by the reference, rejected by reproject(); rendered here once
+                                    lrp_lens_extensions(LRP_LENS_EXT_EQUISOLID) is set */
   LRP_FISHEYE_STEREOGRAPHIC = 3, /* declared by the reference, rejected by reproject() */
   LRP_EQUIRECTANGULAR = 4
 } lrp_lens_type;
+
+/* Opt-in lens extensions (lrp_lens_extensions).  LRP_LENS_EXT_EQUISOLID: LRP_FISHEYE_EQUISOLID, which the reference
+ * declares and rejects, renders on either side.  This project defines its mapping (Blender's equisolid fisheye,
+ * r = 2 f sin(theta / 2)) in binary32, un-fused, associated left to right, with cx, cy the centred sub-sample coordinates:
+ *   equisolid_to_vec:  r_px = sqrtf(cx*cx + cy*cy); r_mm = r_px / img_w * sensor_width;
+ *                      theta = 2.0f * asinf(r_mm / (2.0f * focal_length)); s = sinf(theta) / r_px;
+ *                      x = s * cx; y = s * cy; z = cosf(theta)
+ *   vec_to_equisolid:  x = x / -z; y = y / -z; r = sqrtf(x*x + y*y); theta = atanf(r);
+ *                      r_mm = (2.0f * focal_length) * sinf(0.5f * theta); r_px = r_mm / sensor_width * img_w;
+ *                      cx = x / r * r_px; cy = y / r * r_px
+ * fov and sensor_height do not enter the mapping (in Blender fov only crops the image circle; nothing is masked, as for
+ * every lens of the reference).  The centre pixel of an odd-sized output (r_px == 0) and the pixels beyond the image
+ * circle (r_mm > 2f: asinf gives NaN) have NaN rays and render what the samplers make of NaN coordinates, like the
+ * centre of an equidistant output.  Rays behind the camera fold through x / -z, as for the equidistant source. */
+#define LRP_LENS_EXT_EQUISOLID 1
 
 /* reference src/reproject.hpp:16-20 (enum Interpolation) */
 typedef enum lrp_interpolation { LRP_NEAREST = 0, LRP_BILINEAR = 1, LRP_BICUBIC = 2 } lrp_interpolation;
@@ -100,6 +116,10 @@ typedef struct lrp_post {
 /* ---- library / device ------------------------------------------------------ */
 
 int lrp_abi_version(void);
+/* Process-wide mask of opt-in lens extensions (LRP_LENS_EXT_*), 0 by default: every entry point then rejects the lenses
+ * the reference rejects, with its messages.  Sets the mask for subsequent calls of all threads (each call reads it once)
+ * and returns the previous one; a negative value only queries.  LRP_FISHEYE_STEREOGRAPHIC stays rejected. */
+int lrp_lens_extensions(int mask);
 /* Number of usable HIP devices (0 when there is none; never negative). */
 int lrp_device_count(void);
 /* Static text for a status code. */
@@ -325,6 +345,9 @@ void lrp_lens_equidistant(lrp_lens *lens, float fov);
 void lrp_lens_equirectangular(lrp_lens *lens, float longitude_min, float longitude_max, float latitude_min,
                               float latitude_max);
 void lrp_lens_equirectangular_full(lrp_lens *lens);
+/* equisolid (the LRP_LENS_EXT_EQUISOLID extension): sensor_height = res_y / res_x * sensor_width, as the CLI's --equisolid
+ * (src/main.cpp:45); fov is carried, not used by the mapping. */
+void lrp_lens_equisolid(lrp_lens *lens, float focal_length, float sensor_width, float fov, float res_x, float res_y);
 
 #ifdef __cplusplus
 }

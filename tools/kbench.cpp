@@ -12,6 +12,9 @@
 //   last stream's completion — S = 1 and S = 2 compare back-to-back launches on one stream with launches whose tails and heads may overlap
 //   --batch B: every launch renders B frames (lrp_reproject_batch_device, B <= distinct); times are per launch / B
 //   --geo 0: single launches compute their coordinates in every launch (geometry cache off); --set: lrp_debug_set
+//   --first: before the warm-up, a 256^2 twin of the workload loads its kernels, the caches are released and the workload's first
+//   launch is timed on its own (with the geometry cache on, the launch that fills the entry)
+//   eqs_* workloads: the equisolid lens extension (lrp_lens_extensions), switched on for the run
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -43,7 +46,7 @@
 
 struct Workload {
   const char *name;
-  const char *in_lens, *out_lens; // "rect" | "eqd" | "eqr" | "eqrp"
+  const char *in_lens, *out_lens; // "rect" | "eqd" | "eqr" | "eqrp" | "eqs"
   int interp;
   int has_rot;
   float rot_deg[3];
@@ -76,6 +79,10 @@ static const Workload kWorkloads[] = {
     // general rotation, nearest / bilinear: the plain (unmirrored) path of the tile kernels
     {"eqr_rect_nn_rot", "eqr", "rect", 0, 1, {30, -15, 5}},
     {"eqr_rect_bl_rot", "eqr", "rect", 1, 1, {30, -15, 5}},
+    // the equisolid lens extension: configs[1] with the README's equisolid lens instead of the equidistant stand-in, and the
+    // configs[2] twin (beside eqd_rect_bc / eqr_eqd_bl_rot)
+    {"eqs_rect_bc", "eqs", "rect", 2, 0, {0, 0, 0}},
+    {"eqr_eqs_bl_rot", "eqr", "eqs", 1, 1, {30, -15, 5}},
 };
 
 static void make_lens(lrp_lens *L, const char *kind, int w, int h) {
@@ -83,6 +90,8 @@ static void make_lens(lrp_lens *L, const char *kind, int w, int h) {
     lrp_lens_rectilinear(L, 18.0f, 36.0f, (float)w, (float)h);
   else if (!strcmp(kind, "eqd"))
     lrp_lens_equidistant(L, 3.14159265f);
+  else if (!strcmp(kind, "eqs"))
+    lrp_lens_equisolid(L, 12.5f, 36.0f, 3.14159265f, (float)w, (float)h);
   else if (!strcmp(kind, "eqrp")) {
     float v[4] = {-1.0f, 1.5f, -0.6f, 0.7f};
     if (const char *e = getenv("KBENCH_EQRP")) sscanf(e, "%f,%f,%f,%f", &v[0], &v[1], &v[2], &v[3]);
@@ -104,7 +113,7 @@ static uint64_t fnv1a(const void *p, size_t n) {
 
 int main(int argc, char **argv) {
   int size = 4096, reps = 20, distinct = 4, channels = 4, ns = 1, out_size = 0, warmup = 100, batch = 0, n_streams = 0;
-  bool sum = false, post = false;
+  bool sum = false, post = false, first = false;
   std::vector<std::string> names;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -129,6 +138,7 @@ int main(int argc, char **argv) {
     }
     else if (a == "--sum") sum = true;
     else if (a == "--post") post = true;
+    else if (a == "--first") first = true;
     else names.push_back(a);
   }
   if (!out_size) out_size = size;
@@ -139,6 +149,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "no HIP device\n");
     return 1;
   }
+  lrp_lens_extensions(LRP_LENS_EXT_EQUISOLID); // (the eqs_* workloads; the others do not see the switch)
   HIP_OK(hipSetDevice(0));
   hipStream_t stream;
   HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -241,6 +252,25 @@ int main(int argc, char **argv) {
       printf("%-18s %d streams: %8.1f us per launch (best of 5 runs of %d launches)\n", W->name, n_streams, best * 1e3 / reps, reps);
       for (auto &q : ss) HIP_OK(hipStreamDestroy(q));
       continue;
+    }
+    if (first) { // the first launch of this geometry on its own (caches released: it builds the tables / fills the geometry cache)
+      // a 256^2 twin first, so that the time below holds no one-time loading of the code objects of these kernels
+      lrp_image in_s = in, out_s = out;
+      in_s.data = src[0];
+      out_s.data = dst[0];
+      out_s.width = out_s.height = 256;
+      make_lens(&out_s.lens, W->out_lens, 256, 256);
+      LRP_OKAY(lrp_reproject_device(&in_s, &out_s, ns, W->interp, W->has_rot ? rot : nullptr, post ? &pp : nullptr, 0, stream));
+      HIP_OK(hipStreamSynchronize(stream));
+      lrp_release_cached_tables();
+      HIP_OK(hipStreamSynchronize(stream));
+      HIP_OK(hipEventRecord(e0, stream));
+      launch(0);
+      HIP_OK(hipEventRecord(e1, stream));
+      HIP_OK(hipEventSynchronize(e1));
+      float ms;
+      HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+      printf("%-18s first launch %8.1f us%s\n", W->name, ms * 1e3 / (batch > 0 ? batch : 1), batch > 0 ? " per frame" : "");
     }
     if (batch > 0 && warmup > 100 / batch) warmup = 100 / batch + 2;
     // ~20 ms of back-to-back launches first: the chip settles its clock over ~10 ms of load
