@@ -1,7 +1,8 @@
 // lrp_capi.cpp — the C ABI declared in include/lrp.h: argument validation in the
 // reference's dispatch order, kernel-argument construction, device buffers,
 // streams and the batch context.  Host code only; the kernels live in the
-// lrp_kernels_*.hip / lrp_aux_kernels.hip translation units.
+// lrp_kernels_*.hip / lrp_tile_*.hip / lrp_eqs_*.hip (reprojection), lrp_tables.hip, lrp_geo_lists.hip,
+// lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,21 +21,20 @@
 #include <vector>
 
 #include "../../include/lrp.h"
-#include "lrp_eqs.h"
 #include "lrp_geocache.h"
 #include "lrp_params.h"
 #include "lrp_plan.h"
 #include "lrp_tables.h"
 
 namespace lrp {
-EqsLaunchers g_eqs_launchers = {}; // (lrp_eqs.h: filled in by the units of the equisolid kernels when the library loads)
-hipError_t launch_nearest(const KParams &P, int out_idx, int in_mode, hipStream_t stream);
-hipError_t launch_bilinear(const KParams &P, int out_idx, int in_mode, hipStream_t stream);
-hipError_t launch_bicubic(const KParams &P, int out_idx, int in_mode, hipStream_t stream);
-hipError_t launch_tile_nearest(const KParams &P, int out_idx, int in_mode, hipStream_t stream);
-hipError_t launch_tile_bilinear(const KParams &P, int out_idx, int in_mode, hipStream_t stream);
-hipError_t launch_tile_bicubic(const KParams &P, int out_idx, int in_mode, hipStream_t stream);
-hipError_t launch_win_bicubic(const KParams &P, int out_idx, int in_mode, hipStream_t stream); // (P.geo_mode == 2: the GeoRead kernels)
+// out_lens / in_mode: the ids of lrp_params.h, for every lens (lrp_cells.h)
+hipError_t launch_nearest(const KParams &P, int out_lens, int in_mode, hipStream_t stream);
+hipError_t launch_bilinear(const KParams &P, int out_lens, int in_mode, hipStream_t stream);
+hipError_t launch_bicubic(const KParams &P, int out_lens, int in_mode, hipStream_t stream);
+hipError_t launch_tile_nearest(const KParams &P, int out_lens, int in_mode, hipStream_t stream);
+hipError_t launch_tile_bilinear(const KParams &P, int out_lens, int in_mode, hipStream_t stream);
+hipError_t launch_tile_bicubic(const KParams &P, int out_lens, int in_mode, hipStream_t stream);
+hipError_t launch_win_bicubic(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // (P.geo_mode == 2: the GeoRead kernels)
 hipError_t launch_ss_gather(const KParams &P, int interpolation, int in_mode, hipStream_t stream); // lrp_tile_ssg.hip: nearest / bilinear, num_samples 2-4, from an entry of sub-samples
 hipError_t launch_geo_build_lists(int32_t *box, int out_w, int out_h, int alias_pairs, hipStream_t stream); // lrp_geo_lists.hip
 hipError_t launch_geo_census(int32_t *box, int out_w, int out_h, int in_w, int in_h, bool clear_header, hipStream_t stream); // lrp_geo_lists.hip
@@ -99,12 +99,6 @@ bool lens_in_hot_path(int type, int ext) {
   return type == LRP_RECTILINEAR || type == LRP_FISHEYE_EQUIDISTANT || type == LRP_EQUIRECTANGULAR ||
          (type == LRP_FISHEYE_EQUISOLID && (ext & LRP_LENS_EXT_EQUISOLID) != 0);
 }
-
-// out_idx of the existing kernel tables: 0 rectilinear, 1 equidistant (and the equisolid lens where a table of the radial
-// target stands in for it: the launches that read the geometry cache hold no lens math), 2 equirectangular
-int out_lens_index(int type) { return type == LRP_RECTILINEAR ? 0 : ((type == LRP_FISHEYE_EQUIDISTANT || type == LRP_FISHEYE_EQUISOLID) ? 1 : 2); }
-// the lens ids of lrp_params.h (kRect / kEquidistant / kEquisolid / kEquirect: the numbering of include/lrp.h)
-int out_lens_id(int type) { return type; }
 
 // LoopHorizontally decision, reference src/reproject.cpp:386-394: float span,
 // compared in double against 2*M_PI with a float threshold.
@@ -225,7 +219,7 @@ const KnobSpec kKnobs[kKnobCount] = {
     {"win_tapdma", 0, 1, 1},      // window kernel: passes whose window fits no buffer fetch their taps a quad of lanes per pixel row through LDS-DMA (0: a gather per lane and tap)
     {"geo_census", 0, 1, 1},      // the census of a new geometry-cache entry's windows (lrp_geo_lists.hip; what the automatic choice of the big-window variant reads); 0: not taken
     {"geo_list_recs", 0, 1, 1}, // listed launches: a wavefront reads its block's box record from beside its work-list entry, with the entry (0: from the box array, a second round trip)
-    {"win_ss", 0, 1, 1},              // bicubic with num_samples == 2 through the window kernel's supersampling instantiations (0: the tile kernel, as for any other num_samples > 1)
+    {"win_ss", 0, 1, 1},              // bicubic with num_samples 2-4 through the window kernel's supersampling instantiations (0: the tile kernel, as for any other num_samples > 1)
     {"listed_launches", 0, 0, 0}, // a counter, not a switch: launches rendered by block class so far (set 0 to reset; tests, bench)
     {"big_launches", 0, 0, 0},       // a counter: window launches through the big-window variant so far
 };
@@ -306,8 +300,8 @@ lrp::PlanSwitches plan_switches() {
 lrp::PlanRequest plan_request(const lrp_image *in, const lrp_image *out, int num_samples, int interpolation, const float *rotation,
                               int n_batch, bool band) {
   lrp::PlanRequest r;
-  r.out_type = out_lens_id(out->lens.type);
-  r.in_type = out_lens_id(in->lens.type);
+  r.out_type = out->lens.type; // (the lens ids of lrp_params.h are the numbering of include/lrp.h: asserted below)
+  r.in_type = in->lens.type;
   r.in_mode = in_lens_mode(in->lens);
   r.out_w = out->width, r.out_h = out->height, r.in_w = in->width, r.in_h = in->height, r.channels = out->channels;
   r.num_samples = num_samples, r.interpolation = interpolation;
@@ -324,7 +318,7 @@ static_assert((int)lrp::kPlanRect == (int)lrp::kRect && (int)lrp::kPlanEquidista
               "lrp_plan.h numbers lenses like lrp_params.h");
 static_assert((int)lrp::kRect == LRP_RECTILINEAR && (int)lrp::kEquidistant == LRP_FISHEYE_EQUIDISTANT && (int)lrp::kEquisolid == LRP_FISHEYE_EQUISOLID &&
                   (int)lrp::kEquirect == LRP_EQUIRECTANGULAR,
-              "lrp_params.h numbers lenses like include/lrp.h (out_lens_id)");
+              "lrp_params.h numbers lenses like include/lrp.h");
 static_assert((int)lrp::kPlanInRect == (int)lrp::kInRect && (int)lrp::kPlanInEquidistant == (int)lrp::kInEquidistant &&
                   (int)lrp::kPlanInEquirect == (int)lrp::kInEquirect && (int)lrp::kPlanInEquirectLoop == (int)lrp::kInEquirectLoop &&
                   (int)lrp::kPlanInEquisolid == (int)lrp::kInEquisolid,
@@ -343,13 +337,7 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
     P.y_offset = row_first;
     P.y_end = row_first + row_count;
   }
-  const int oi = out_lens_index(out->lens.type);
-  const int im = in_lens_mode(in->lens);
-  // The equisolid lens (either side): its own kernels (lrp_eqs.h) — except where the geometry cache is read: those kernels
-  // hold no lens math, and the clamped, non-wrapping equidistant source's instantiation serves (im_std).
-  const int out_id = out_lens_id(out->lens.type);
-  const bool eqs = lrp::eqs_cell(out_id, im) >= 0;
-  const int im_std = im == lrp::kInEquisolid ? lrp::kInEquidistant : im;
+  const int ol = out->lens.type, im = in_lens_mode(in->lens); // the cell of this call (lrp_cells.h)
   hipError_t e;
   lrp::TableLease lease; // pins the cached tables until every launch of this call is enqueued (scope end)
   lrp::GeoUse geo;       // this launch's use of the geometry cache (none unless set below)
@@ -396,7 +384,7 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
       lrp::GeoKey key;
       std::memset(&key, 0, sizeof(key));
       key.device = device;
-      key.out_type = out_id;
+      key.out_type = ol;
       key.in_mode = im;
       key.out_w = out->width, key.out_h = out->height, key.in_w = in->width, key.in_h = in->height;
       key.has_rot = P.has_rot;
@@ -440,15 +428,11 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
         }
       }
       if (window && P.geo_mode == 2 && P.big_windows != 0) g_knobs[kKnobBigLaunches].fetch_add(1, std::memory_order_relaxed);
-      if (eqs && P.geo_mode != 2) {
-        const lrp::EqsLaunchFn fn = window ? lrp::g_eqs_launchers.win : lrp::g_eqs_launchers.tile[interpolation];
-        return fn ? fn(P, out_id, im, stream) : hipErrorInvalidDeviceFunction;
-      }
-      if (window) return lrp::launch_win_bicubic(P, oi, im_std, stream);
-      if (P.geo_mode == 2 && num_samples > 1) return lrp::launch_ss_gather(P, interpolation, im_std, stream); // (a lane per sub-sample: coalesced loads of the entry)
-      if (interpolation == LRP_NEAREST) return lrp::launch_tile_nearest(P, oi, im_std, stream);
-      if (interpolation == LRP_BILINEAR) return lrp::launch_tile_bilinear(P, oi, im_std, stream);
-      return lrp::launch_tile_bicubic(P, oi, im_std, stream);
+      if (window) return lrp::launch_win_bicubic(P, ol, im, stream);
+      if (P.geo_mode == 2 && num_samples > 1) return lrp::launch_ss_gather(P, interpolation, im, stream); // (a lane per sub-sample: coalesced loads of the entry)
+      if (interpolation == LRP_NEAREST) return lrp::launch_tile_nearest(P, ol, im, stream);
+      if (interpolation == LRP_BILINEAR) return lrp::launch_tile_bilinear(P, ol, im, stream);
+      return lrp::launch_tile_bicubic(P, ol, im, stream);
     };
     if (n_batch <= 0) {
       e = launch();
@@ -502,14 +486,12 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
         P.dst = out[i].data + c0;
         P.ch_count = std::min(group, C - c0);
         P.has_post = post != nullptr && c0 == 0;
-        if (eqs)
-          e = lrp::g_eqs_launchers.pixel ? lrp::g_eqs_launchers.pixel(P, interpolation, out_id, im, stream) : hipErrorInvalidDeviceFunction;
-        else if (interpolation == LRP_NEAREST)
-          e = lrp::launch_nearest(P, oi, im, stream);
+        if (interpolation == LRP_NEAREST)
+          e = lrp::launch_nearest(P, ol, im, stream);
         else if (interpolation == LRP_BILINEAR)
-          e = lrp::launch_bilinear(P, oi, im, stream);
+          e = lrp::launch_bilinear(P, ol, im, stream);
         else
-          e = lrp::launch_bicubic(P, oi, im, stream);
+          e = lrp::launch_bicubic(P, ol, im, stream);
       }
   }
   if (e != hipSuccess) return hip_fail(e, "reproject kernel launch");

@@ -1,11 +1,8 @@
-// lrp_eqs_tile_bc.hip — bicubic instantiations of the tile kernel for the equisolid cells (lrp_eqs_tile.h).
-#include "lrp_eqs_tile.h"
+// lrp_eqs_tile_bc.hip — bicubic instantiations of the tile kernel (lrp_kernel_v2.h): the equisolid cells.
+#include "lrp_kernel_v2.h"
 
 namespace lrp {
-namespace {
-hipError_t launch_eqs_tile_bicubic(const KParams &P, int out_lens, int in_mode, hipStream_t stream) {
-  return launch_eqs_tile<2>(P, out_lens, in_mode, stream);
+hipError_t launch_tile_bicubic_eqs(const KParams &P, int out_lens, int in_mode, hipStream_t stream) {
+  return launch_tile_interp<2, kEqsCells>(P, out_lens, in_mode, stream);
 }
-const bool g_registered = (g_eqs_launchers.tile[2] = launch_eqs_tile_bicubic, true);
-} // namespace
 } // namespace lrp

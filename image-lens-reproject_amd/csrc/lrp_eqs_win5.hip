@@ -1,8 +1,8 @@
-// lrp_eqs_win5.hip — window-kernel instantiations for the equisolid cells (lrp_eqs_win.h): 5 channels, one sample per pixel.
-#include "lrp_eqs_win.h"
+// lrp_eqs_win5.hip — bicubic window-kernel instantiations (lrp_kernel_v2.h): RGBAZ, plain blocks, the equisolid cells.
+#include "lrp_kernel_v2.h"
 
 namespace lrp {
-hipError_t launch_eqs_win_c5(const KParams &P, int out_lens, int in_mode, hipStream_t stream) {
-  return launch_eqs_win_impl<5, false>(P, out_lens, in_mode, stream);
+hipError_t launch_win_bicubic_c5_m0_eqs(const KParams &P, int out_lens, int in_mode, hipStream_t stream) {
+  return launch_win_bicubic_impl<0, 5, false, false, kEqsCells>(P, out_lens, in_mode, stream);
 }
 } // namespace lrp

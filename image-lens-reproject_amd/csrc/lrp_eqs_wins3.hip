@@ -1,8 +1,8 @@
-// lrp_eqs_wins3.hip — window-kernel instantiations for the equisolid cells (lrp_eqs_win.h): 3 channels, num_samples 2-4.
-#include "lrp_eqs_win.h"
+// lrp_eqs_wins3.hip — bicubic window-kernel instantiations (lrp_kernel_v2.h): RGB, num_samples 2-4 (the SS instantiations), the equisolid cells.
+#include "lrp_kernel_v2.h"
 
 namespace lrp {
-hipError_t launch_eqs_win_ss_c3(const KParams &P, int out_lens, int in_mode, hipStream_t stream) {
-  return launch_eqs_win_impl<3, true>(P, out_lens, in_mode, stream);
+hipError_t launch_win_bicubic_ss_c3_eqs(const KParams &P, int out_lens, int in_mode, hipStream_t stream) {
+  return launch_win_bicubic_impl<0, 3, false, true, kEqsCells>(P, out_lens, in_mode, stream);
 }
 } // namespace lrp

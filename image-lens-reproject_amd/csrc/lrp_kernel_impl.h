@@ -12,6 +12,7 @@
 // hit in that XCD's private 4 MiB L2.
 #pragma once
 
+#include "lrp_cells.h"
 #include "lrp_device.h"
 
 namespace lrp {
@@ -63,42 +64,25 @@ __global__ __launch_bounds__(kThreads) void reproject_kernel(const KParams P) {
   store_texel<CH>(P.dst, off, acc, P.ch_count);
 }
 
-using KernelFn = void (*)(const KParams);
-
-template <int Interp, int CH> struct KernelTable {
-  // [out lens 0..2][in mode 0..3]
-  static KernelFn get(int out_idx, int in_mode) {
-    static const KernelFn table[3][4] = {
-        {reproject_kernel<kRect, kInRect, Interp, CH>, reproject_kernel<kRect, kInEquidistant, Interp, CH>,
-         reproject_kernel<kRect, kInEquirect, Interp, CH>, reproject_kernel<kRect, kInEquirectLoop, Interp, CH>},
-        {reproject_kernel<kEquidistant, kInRect, Interp, CH>,
-         reproject_kernel<kEquidistant, kInEquidistant, Interp, CH>,
-         reproject_kernel<kEquidistant, kInEquirect, Interp, CH>,
-         reproject_kernel<kEquidistant, kInEquirectLoop, Interp, CH>},
-        {reproject_kernel<kEquirect, kInRect, Interp, CH>, reproject_kernel<kEquirect, kInEquidistant, Interp, CH>,
-         reproject_kernel<kEquirect, kInEquirect, Interp, CH>,
-         reproject_kernel<kEquirect, kInEquirectLoop, Interp, CH>}};
-    return table[out_idx][in_mode];
+// The cells of the pixel kernel: all of them.  Set: the ones this unit compiles (lrp_cells.h).
+template <int Interp, int CH, CellSet Set> struct PixelCell {
+  template <int OutLens, int InMode> static constexpr KernelFn kernel() {
+    if constexpr (in_cell_set(Set, OutLens, InMode))
+      return reproject_kernel<OutLens, InMode, Interp, CH>;
+    else
+      return nullptr;
   }
 };
 
-// The kernel of a launch: from the table above (out_idx: 0 rectilinear, 1 equidistant, 2 equirectangular), or from the
-// table of a unit of its own (Pick, the equisolid lens: lrp_eqs_pixel.hip).  Only the picked table is instantiated.
-template <int Interp> struct KernelTablePick {
-  static KernelFn get(const KParams &P, int out_idx, int in_mode) {
-    return (P.channels == 4) ? KernelTable<Interp, 4>::get(out_idx, in_mode) : KernelTable<Interp, 0>::get(out_idx, in_mode);
-  }
-};
-
-template <int Interp, class Pick = KernelTablePick<Interp>>
-hipError_t launch_interp(KParams P, int out_idx, int in_mode, hipStream_t stream) {
+template <int Interp, CellSet Set = kStdCells>
+hipError_t launch_interp(KParams P, int out_lens, int in_mode, hipStream_t stream) {
   P.tiles_x = (P.out_w + kTileW - 1) / kTileW;
   const int rows = P.y_end - P.y_offset;
   P.tiles_y = (rows + kTileH - 1) / kTileH;
   const int n_tiles = P.tiles_x * P.tiles_y;
   if (n_tiles <= 0) return hipSuccess;
   const dim3 grid((unsigned)(kXcds * xcd_rows(P.tiles_y) * P.tiles_x)), block(kThreads);
-  KernelFn fn = Pick::get(P, out_idx, in_mode);
+  const KernelFn fn = P.channels == 4 ? cell_kernel<PixelCell<Interp, 4, Set>>(out_lens, in_mode) : cell_kernel<PixelCell<Interp, 0, Set>>(out_lens, in_mode);
   if (!fn) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, grid, block, 0, stream, P);
   return hipGetLastError();

@@ -36,7 +36,7 @@
 //   Windows larger than the LDS budget (poles, seam, strong minification) and non-consecutive
 //   taps fall back, per wavefront, to explicit per-tap addressing.
 //
-// Files: lrp_kernel_common.h (shared device code), lrp_tile_kernel.h (tile kernel + launcher), lrp_win_kernel.h (window
+// Files: lrp_cells.h (the kernel table by lens ids), lrp_kernel_common.h (shared device code), lrp_tile_kernel.h (tile kernel + launcher), lrp_win_kernel.h (window
 // kernel + launcher).  Translation units include this umbrella.
 #pragma once
 

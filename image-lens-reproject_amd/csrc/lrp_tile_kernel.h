@@ -1,6 +1,7 @@
 // lrp_tile_kernel.h — the tile kernel (nearest, bilinear, super-sampled / RGBAZ bicubic) and its launcher.
 #pragma once
 
+#include "lrp_cells.h"
 #include "lrp_kernel_common.h"
 
 namespace lrp {
@@ -261,65 +262,55 @@ __global__ __launch_bounds__(kT2Threads, (Frames || GeoRead) ? LRP_TILE_MINWAVES
   }
 }
 
-using TileKernelFn = void (*)(const KParams);
+using TileKernelFn = KernelFn;
 
+// The cells of the tile kernel (lrp_cells.h): all of them; with the frame loop, the ones that have it.  Set: the ones this
+// unit compiles.
+template <int Interp, int CH, bool Frames, CellSet Set> struct TileCell {
+  template <int OutLens, int InMode> static constexpr TileKernelFn kernel() {
+    if constexpr (in_cell_set(Set, OutLens, InMode) && (!Frames || frame_loop_cell(OutLens, InMode)))
+      return reproject_tile_kernel<OutLens, InMode, Interp, CH, Frames>;
+    else
+      return nullptr;
+  }
+};
 // The GeoRead tile kernels: one per source mode.
-template <int Interp, int CH> struct TileGeoKernelTable {
-  static TileKernelFn get(int in_mode) {
-    static_assert(Interp != 2, "nearest / bilinear");
-    static const TileKernelFn table[4] = {
-        reproject_tile_kernel<kRect, kInRect, Interp, CH, false, true>, reproject_tile_kernel<kRect, kInEquidistant, Interp, CH, false, true>,
-        reproject_tile_kernel<kRect, kInEquirect, Interp, CH, false, true>, reproject_tile_kernel<kRect, kInEquirectLoop, Interp, CH, false, true>};
-    return table[in_mode];
+template <int Interp, int CH, CellSet Set> struct TileGeoCell {
+  template <int OutLens, int InMode> static constexpr TileKernelFn kernel() {
+    if constexpr (in_cell_set(Set, OutLens, InMode) && geo_read_cell(OutLens, InMode))
+      return reproject_tile_kernel<OutLens, InMode, Interp, CH, false, true>;
+    else
+      return nullptr;
   }
 };
 
-template <int Interp, int CH, bool Frames> struct TileKernelTable {
-  static TileKernelFn get(int out_idx, int in_mode) {
-    static const TileKernelFn table[3][4] = {
-        {reproject_tile_kernel<kRect, kInRect, Interp, CH, Frames>, reproject_tile_kernel<kRect, kInEquidistant, Interp, CH, Frames>,
-         reproject_tile_kernel<kRect, kInEquirect, Interp, CH, Frames>, reproject_tile_kernel<kRect, kInEquirectLoop, Interp, CH, Frames>},
-        {reproject_tile_kernel<kEquidistant, kInRect, Interp, CH, Frames>,
-         reproject_tile_kernel<kEquidistant, kInEquidistant, Interp, CH, Frames>,
-         reproject_tile_kernel<kEquidistant, kInEquirect, Interp, CH, Frames>,
-         reproject_tile_kernel<kEquidistant, kInEquirectLoop, Interp, CH, Frames>},
-        {reproject_tile_kernel<kEquirect, kInRect, Interp, CH, Frames>, reproject_tile_kernel<kEquirect, kInEquidistant, Interp, CH, Frames>,
-         reproject_tile_kernel<kEquirect, kInEquirect, Interp, CH, Frames>,
-         reproject_tile_kernel<kEquirect, kInEquirectLoop, Interp, CH, Frames>}};
-    return table[out_idx][in_mode];
-  }
-};
-
-// The kernel of a launch (P.frames_per_wave and P.geo_mode set): from the tables above, or — Pick of the equisolid lens,
-// lrp_eqs_tile.h — from the table of a unit of its own.  Only the picked tables are instantiated.  kFrameLoop false: the
-// picker has no frame-loop instantiations, a batch renders a frame per workgroup row (blockIdx.y).
-template <int Interp> struct TileTablePick {
-  static constexpr bool kFrameLoop = true;
-  static TileKernelFn get(const KParams &P, int out_idx, int in_mode) {
-    if (P.geo_mode == 2) { // coordinates from the geometry cache (the host asks for it for single whole-image launches only)
-      if constexpr (Interp != 2) {
-        if (P.quad != 0 || P.num_samples != 1 || P.y_offset != 0 || P.y_end != P.out_h) return nullptr;
-        return P.channels == 4 ? TileGeoKernelTable<Interp, 4>::get(in_mode) : P.channels == 3 ? TileGeoKernelTable<Interp, 3>::get(in_mode) : TileGeoKernelTable<Interp, 5>::get(in_mode);
-      } else {
-        return nullptr;
-      }
-    } else if (P.frames_per_wave > 1) {
-      if constexpr (Interp != 2)
-        return P.channels == 4   ? TileKernelTable<Interp, 4, true>::get(out_idx, in_mode)
-               : P.channels == 3 ? TileKernelTable<Interp, 3, true>::get(out_idx, in_mode)
-                                 : TileKernelTable<Interp, 5, true>::get(out_idx, in_mode);
-      else
-        return nullptr;
+// The kernel of a launch (P.frames_per_wave and P.geo_mode set); nullptr: there is none.
+template <int Interp, int CH, CellSet Set> TileKernelFn tile_kernel_ch(const KParams &P, int out_lens, int in_mode) {
+  if (P.quad != 0 && !mirror_cell(1, out_lens, in_mode)) return nullptr; // (mirrored pixels / rays: the reference's lenses)
+  if (P.geo_mode == 2) { // coordinates from the geometry cache (the host asks for it for single whole-image launches only)
+    if constexpr (Interp != 2) {
+      if (P.quad != 0 || P.num_samples != 1 || P.y_offset != 0 || P.y_end != P.out_h) return nullptr;
+      return cell_kernel<TileGeoCell<Interp, CH, Set>>(kRect, geo_read_in_mode(in_mode));
     } else {
-      return P.channels == 4   ? TileKernelTable<Interp, 4, false>::get(out_idx, in_mode)
-             : P.channels == 3 ? TileKernelTable<Interp, 3, false>::get(out_idx, in_mode)
-                               : TileKernelTable<Interp, 5, false>::get(out_idx, in_mode);
+      return nullptr;
     }
+  } else if (P.frames_per_wave > 1) {
+    if constexpr (Interp != 2)
+      return cell_kernel<TileCell<Interp, CH, true, Set>>(out_lens, in_mode);
+    else
+      return nullptr;
+  } else {
+    return cell_kernel<TileCell<Interp, CH, false, Set>>(out_lens, in_mode);
   }
-};
+}
+template <int Interp, CellSet Set> TileKernelFn tile_kernel(const KParams &P, int out_lens, int in_mode) {
+  return P.channels == 4   ? tile_kernel_ch<Interp, 4, Set>(P, out_lens, in_mode)
+         : P.channels == 3 ? tile_kernel_ch<Interp, 3, Set>(P, out_lens, in_mode)
+                           : tile_kernel_ch<Interp, 5, Set>(P, out_lens, in_mode);
+}
 
 // P.channels must be 3, 4 or 5.
-template <int Interp, class Pick = TileTablePick<Interp>> hipError_t launch_tile_interp(KParams P, int out_idx, int in_mode, hipStream_t stream) {
+template <int Interp, CellSet Set = kStdCells> hipError_t launch_tile_interp(KParams P, int out_lens, int in_mode, hipStream_t stream) {
   constexpr int tile_h = tile_rows<Interp>() * kT2Waves;
   if (P.quad) { // the top-left quadrant only: every pixel also renders its three mirror images
     P.tiles_x = ((P.out_w + 1) / 2 + kT2W - 1) / kT2W;
@@ -339,13 +330,13 @@ template <int Interp, class Pick = TileTablePick<Interp>> hipError_t launch_tile
   if (Interp != 2 && P.num_samples == 1 && P.batch_n > 1 && P.quad == 0 && P.geo_mode != 2) { // (the plain path: any rotation; the mirrored paths are bound by memory; GeoRead: a frame per workgroup)
     const long long units = (long long)n_tiles * P.batch_n;
     int F = (int)std::min<long long>(P.batch_n, std::max<long long>(1, units / 4096));
-    if (out_idx == 2 && in_mode == kInRect) F = 1; // (see the window kernel: uneven tiles)
+    if (out_lens == kEquirect && in_mode == kInRect) F = 1; // (see the window kernel: uneven tiles)
     if (frames_override > 0) F = std::max(1, std::min(P.batch_n, frames_override)); // the caller's override (lrp_debug_set "batch_frames": A/B runs, tests)
-    if (!Pick::kFrameLoop) F = 1;
     P.frames_per_wave = F;
+    if (F > 1 && !tile_kernel<Interp, Set>(P, out_lens, in_mode)) P.frames_per_wave = F = 1; // no frame loop for this cell: a frame per workgroup row
     groups = (P.batch_n + F - 1) / F;
   }
-  const TileKernelFn fn = Pick::get(P, out_idx, in_mode);
+  const TileKernelFn fn = tile_kernel<Interp, Set>(P, out_lens, in_mode);
   if (!fn) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3((unsigned)(kXcds * xcd_rows(P.tiles_y) * P.tiles_x), (unsigned)groups), dim3(kT2Threads), 0, stream, P);
   return hipGetLastError();

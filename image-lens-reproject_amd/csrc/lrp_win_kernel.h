@@ -1457,105 +1457,59 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
 #endif
 }
 
-// The window kernel of one (output lens, source mode) cell for a mirror mode, or null where the mode does not exist
-// (rows-only needs the column-separable source x: no equidistant lens on either side; columns-only a rectilinear target).
-template <int OutLens, int InMode, int QMode, int CH, bool Frames> constexpr TileKernelFn win_kernel_fn() {
-  if constexpr (QMode == 2 && (OutLens == kEquidistant || InMode == kInEquidistant))
-    return nullptr;
-  else if constexpr (QMode == 3 && OutLens != kRect)
-    return nullptr;
-  else if constexpr (QMode == 4 && OutLens != kEquidistant)
-    return nullptr;
-  else
-    return reproject_bicubic_win_kernel<OutLens, InMode, QMode, CH, Frames>;
-}
-template <int QMode, int CH, bool Frames> struct WinKernelTable {
-  static TileKernelFn get(int out_idx, int in_mode) {
-    static const TileKernelFn table[3][4] = {
-        {win_kernel_fn<kRect, kInRect, QMode, CH, Frames>(), win_kernel_fn<kRect, kInEquidistant, QMode, CH, Frames>(),
-         win_kernel_fn<kRect, kInEquirect, QMode, CH, Frames>(), win_kernel_fn<kRect, kInEquirectLoop, QMode, CH, Frames>()},
-        {win_kernel_fn<kEquidistant, kInRect, QMode, CH, Frames>(), win_kernel_fn<kEquidistant, kInEquidistant, QMode, CH, Frames>(),
-         win_kernel_fn<kEquidistant, kInEquirect, QMode, CH, Frames>(), win_kernel_fn<kEquidistant, kInEquirectLoop, QMode, CH, Frames>()},
-        {win_kernel_fn<kEquirect, kInRect, QMode, CH, Frames>(), win_kernel_fn<kEquirect, kInEquidistant, QMode, CH, Frames>(),
-         win_kernel_fn<kEquirect, kInEquirect, QMode, CH, Frames>(), win_kernel_fn<kEquirect, kInEquirectLoop, QMode, CH, Frames>()}};
-    return table[out_idx][in_mode];
+// The cells of the window kernel (lrp_cells.h): the ones where the mirror mode exists (plain blocks, the supersampling
+// instantiations — num_samples 2-4, plain blocks —: all of them); with the frame loop, the ones that have it.  Set: the ones
+// this unit compiles.
+template <int QMode, int CH, bool Frames, bool SS, CellSet Set> struct WinCell {
+  template <int OutLens, int InMode> static constexpr TileKernelFn kernel() {
+    if constexpr (in_cell_set(Set, OutLens, InMode) && mirror_cell(QMode, OutLens, InMode) && (!Frames || frame_loop_cell(OutLens, InMode)))
+      return reproject_bicubic_win_kernel<OutLens, InMode, QMode, CH, Frames, false, SS>;
+    else
+      return nullptr;
   }
 };
-
 // The GeoRead instantiations (plain blocks, coordinates from the geometry cache): one per source mode.
 // ... and with the frame loop: batched launches of a geometry whose entry exists.  A wavefront loads the coordinates and the
 // extremes of its block once and renders it for up to 16 frames (same box, 16-frame launches: headline 104.3 -> 100.9 us per
 // frame, general rotation 98.3 -> 95.7 against the instantiations that compute their coordinates once per 16 frames — those
 // carry the lens math in registers: 68-90 spilled SGPRs against 11-22 here).
-template <int CH> struct WinGeoFramesKernelTable {
-  static TileKernelFn get(int in_mode) {
-    static const TileKernelFn table[4] = {
-        reproject_bicubic_win_kernel<kRect, kInRect, 0, CH, true, true>, reproject_bicubic_win_kernel<kRect, kInEquidistant, 0, CH, true, true>,
-        reproject_bicubic_win_kernel<kRect, kInEquirect, 0, CH, true, true>, reproject_bicubic_win_kernel<kRect, kInEquirectLoop, 0, CH, true, true>};
-    return table[in_mode];
-  }
-};
-template <int CH> struct WinGeoKernelTable {
-  static TileKernelFn get(int in_mode, bool big_windows) {
-    static const TileKernelFn table[4] = {
-        reproject_bicubic_win_kernel<kRect, kInRect, 0, CH, false, true>, reproject_bicubic_win_kernel<kRect, kInEquidistant, 0, CH, false, true>,
-        reproject_bicubic_win_kernel<kRect, kInEquirect, 0, CH, false, true>, reproject_bicubic_win_kernel<kRect, kInEquirectLoop, 0, CH, false, true>};
-    if (big_windows && in_mode == kInRect) return reproject_bicubic_win_kernel<kEquirect, kInRect, 0, CH, false, true>;
-    // ... and of the panorama sources, for geometries whose census says so (lrp_capi.cpp kBigWidePercent)
-    if (big_windows && in_mode == kInEquirect) return reproject_bicubic_win_kernel<kEquirect, kInEquirect, 0, CH, false, true>;
-    if (big_windows && in_mode == kInEquirectLoop) return reproject_bicubic_win_kernel<kEquirect, kInEquirectLoop, 0, CH, false, true>;
-    // (round 4, without tap DMA: the pole face of the 8192^2 -> 2048^2 cubemap 108.6 -> 103.9 us, its side faces 59.8 -> 67.2, every
-    // 4096^2 mapping out of a panorama 20-25 % slower; round 5 with tap DMA: pole face 97 -> 80, side faces 48 -> 60 — hence per geometry)
-    return table[in_mode];
+// ... and the big-window variants of the single launches (the rectilinear source; the panorama sources, for geometries whose
+// census says so: lrp_capi.cpp kBigWidePercent).
+// (round 4, without tap DMA: the pole face of the 8192^2 -> 2048^2 cubemap 108.6 -> 103.9 us, its side faces 59.8 -> 67.2, every
+// 4096^2 mapping out of a panorama 20-25 % slower; round 5 with tap DMA: pole face 97 -> 80, side faces 48 -> 60 — hence per geometry)
+// SS: the ones that read an entry of sub-samples.
+template <int CH, bool Frames, bool SS, CellSet Set> struct WinGeoCell {
+  template <int OutLens, int InMode> static constexpr TileKernelFn kernel() {
+    if constexpr (in_cell_set(Set, OutLens, InMode) && (geo_read_cell(OutLens, InMode) || (!Frames && !SS && geo_big_cell(OutLens, InMode))))
+      return reproject_bicubic_win_kernel<OutLens, InMode, 0, CH, Frames, true, SS>;
+    else
+      return nullptr;
   }
 };
 
-// The supersampling instantiations (num_samples == 2): plain blocks, one per (output lens, source mode) cell.
-template <int CH> struct WinSSKernelTable {
-  static TileKernelFn get(int out_idx, int in_mode) {
-    static const TileKernelFn table[3][4] = {
-        {reproject_bicubic_win_kernel<kRect, kInRect, 0, CH, false, false, true>, reproject_bicubic_win_kernel<kRect, kInEquidistant, 0, CH, false, false, true>,
-         reproject_bicubic_win_kernel<kRect, kInEquirect, 0, CH, false, false, true>, reproject_bicubic_win_kernel<kRect, kInEquirectLoop, 0, CH, false, false, true>},
-        {reproject_bicubic_win_kernel<kEquidistant, kInRect, 0, CH, false, false, true>, reproject_bicubic_win_kernel<kEquidistant, kInEquidistant, 0, CH, false, false, true>,
-         reproject_bicubic_win_kernel<kEquidistant, kInEquirect, 0, CH, false, false, true>, reproject_bicubic_win_kernel<kEquidistant, kInEquirectLoop, 0, CH, false, false, true>},
-        {reproject_bicubic_win_kernel<kEquirect, kInRect, 0, CH, false, false, true>, reproject_bicubic_win_kernel<kEquirect, kInEquidistant, 0, CH, false, false, true>,
-         reproject_bicubic_win_kernel<kEquirect, kInEquirect, 0, CH, false, false, true>, reproject_bicubic_win_kernel<kEquirect, kInEquirectLoop, 0, CH, false, false, true>}};
-    return table[out_idx][in_mode];
+// The kernel of a launch (P.frames_per_wave set); nullptr: there is none.
+template <int QMode, int CH, bool GeoRead, bool SS, CellSet Set> TileKernelFn win_kernel(const KParams &P, int out_lens, int in_mode) {
+  if constexpr (GeoRead) {
+    const int im = geo_read_in_mode(in_mode);
+    if constexpr (SS)
+      return cell_kernel<WinGeoCell<CH, false, true, Set>>(kRect, im);
+    else if (P.frames_per_wave > 1)
+      return cell_kernel<WinGeoCell<CH, true, false, Set>>(kRect, im);
+    else
+      return cell_kernel<WinGeoCell<CH, false, false, Set>>((P.big_windows != 0 && geo_big_cell(kEquirect, im)) ? kEquirect : kRect, im);
+  } else if constexpr (SS) {
+    return cell_kernel<WinCell<0, CH, false, true, Set>>(out_lens, in_mode);
+  } else {
+    return P.frames_per_wave > 1 ? cell_kernel<WinCell<QMode, CH, true, false, Set>>(out_lens, in_mode)
+                                 : cell_kernel<WinCell<QMode, CH, false, false, Set>>(out_lens, in_mode);
   }
-};
-
-// ... and the ones that read an entry of sub-samples from the geometry cache: one per source mode.
-template <int CH> struct WinSSGeoKernelTable {
-  static TileKernelFn get(int in_mode) {
-    static const TileKernelFn table[4] = {
-        reproject_bicubic_win_kernel<kRect, kInRect, 0, CH, false, true, true>, reproject_bicubic_win_kernel<kRect, kInEquidistant, 0, CH, false, true, true>,
-        reproject_bicubic_win_kernel<kRect, kInEquirect, 0, CH, false, true, true>, reproject_bicubic_win_kernel<kRect, kInEquirectLoop, 0, CH, false, true, true>};
-    return table[in_mode];
-  }
-};
+}
 
 // num_samples must be 1 — or 2, 3, 4 for the SS launcher (a lane per sub-sample).
 // QMode != 0: P.win_mode == QMode, set by the host only for cells where the mode exists.  GeoRead: P.geo_mode == 2, a single
 // whole-image launch.
-// The kernel of a launch (P.frames_per_wave set): from the tables above, or — Pick of the equisolid lens, lrp_eqs_win.h —
-// from the table of a unit of its own.  Only the picked table is instantiated.  kFrameLoop false: the picker has no
-// frame-loop instantiations, a batch renders a frame per workgroup row (blockIdx.y).
-template <int QMode, int CH, bool GeoRead, bool SS> struct WinTablePick {
-  static constexpr bool kFrameLoop = true;
-  static TileKernelFn get(const KParams &P, int out_idx, int in_mode) {
-    if constexpr (SS && GeoRead)
-      return WinSSGeoKernelTable<CH>::get(in_mode);
-    else if constexpr (SS)
-      return WinSSKernelTable<CH>::get(out_idx, in_mode);
-    else if constexpr (GeoRead)
-      return P.frames_per_wave > 1 ? WinGeoFramesKernelTable<CH>::get(in_mode) : WinGeoKernelTable<CH>::get(in_mode, P.big_windows != 0);
-    else
-      return P.frames_per_wave > 1 ? WinKernelTable<QMode, CH, true>::get(out_idx, in_mode) : WinKernelTable<QMode, CH, false>::get(out_idx, in_mode);
-  }
-};
-
-template <int QMode, int CH, bool GeoRead = false, bool SS = false, class Pick = WinTablePick<QMode, CH, GeoRead, SS>>
-inline hipError_t launch_win_bicubic_impl(KParams P, int out_idx, int in_mode, hipStream_t stream) {
+template <int QMode, int CH, bool GeoRead = false, bool SS = false, CellSet Set = kStdCells>
+inline hipError_t launch_win_bicubic_impl(KParams P, int out_lens, int in_mode, hipStream_t stream) {
   static_assert(!GeoRead || QMode == 0, "the geometry cache feeds plain blocks");
   static_assert(!SS || QMode == 0, "supersampling: plain blocks");
   if (GeoRead && (P.geo_mode != 2 || P.y_offset != 0 || P.y_end != P.out_h)) return hipErrorInvalidValue;
@@ -1582,7 +1536,7 @@ inline hipError_t launch_win_bicubic_impl(KParams P, int out_idx, int in_mode, h
     if (GeoRead && !SS && P.blocks_per_wave > 0) G = std::min(P.blocks_per_wave, kGeoStripRows); // the caller's override (lrp_debug_set "geo_strip")
     // (a batch whose wavefronts walk several frames pipelines the windows of one block across its frames: one block per
     // wavefront measured 2-3 % faster there — equirect -> fisheye rotated 143 -> 139 us, rect -> rect 130.5 -> 128 —, four 5 % slower)
-    if (P.batch_n > 1 && !(out_idx == 2 && in_mode == kInRect)) G = 1;
+    if (P.batch_n > 1 && !(out_lens == kEquirect && in_mode == kInRect)) G = 1;
     const bool strip_forced = GeoRead && !SS && P.blocks_per_wave > 0;
     // (a rectilinear source under a rectilinear / fisheye target: half of the blocks are corner blocks, the rest wait for
     // gathers or edge rows — single blocks balance the launch: rect -> fisheye single launches 164 -> 154 us)
@@ -1608,15 +1562,16 @@ inline hipError_t launch_win_bicubic_impl(KParams P, int out_idx, int in_mode, h
     int F = (int)std::min<long long>(P.batch_n, std::max<long long>(1, units / 8192));
     // a rectilinear view inside a panorama: a quarter of the strips (the ones in view) carry most of the frame's time and
     // gain nothing from shared coordinates (they wait for gathers) — 16 frames long they unbalance the launch (223 -> 256 us)
-    if (out_idx == 2 && in_mode == kInRect) F = 1;
+    if (out_lens == kEquirect && in_mode == kInRect) F = 1;
     if (GeoRead && P.big_windows != 0) F = 1; // (the big-window variant has no frame loop: a wavefront per block and frame)
     if (frames_override > 0) F = std::max(1, std::min(P.batch_n, frames_override)); // the caller's override (lrp_debug_set "batch_frames": A/B runs, tests)
     if (P.geo_mode == 1 || P.geo_mode == 3) F = 1; // the launch that writes a geometry-cache entry: the instantiations without the frame loop have the side output
-    if (SS || !Pick::kFrameLoop) F = 1;
+    if (SS) F = 1;
     P.frames_per_wave = F;
+    if (F > 1 && !win_kernel<QMode, CH, GeoRead, SS, Set>(P, out_lens, in_mode)) P.frames_per_wave = F = 1; // no frame loop for this cell: a frame per workgroup row
     groups = (P.batch_n + F - 1) / F;
   }
-  const TileKernelFn fn = Pick::get(P, out_idx, in_mode);
+  const TileKernelFn fn = win_kernel<QMode, CH, GeoRead, SS, Set>(P, out_lens, in_mode);
   if (!fn) return hipErrorInvalidValue; // (the host never asks for a mode outside its cells)
   unsigned grid_x = (unsigned)(kXcds * xcd_rows(P.tiles_y, kWinXcdBand) * P.tiles_x);
   if (GeoRead && P.geo_work != nullptr) {
