@@ -207,10 +207,10 @@ const KnobSpec kKnobs[kKnobCount] = {
     {"mirror_modes", 0, 1, 1},  // window kernel: pan / pitch / shared-ray mirror modes
     {"win_edge", 0, 1, 1},          // window kernel: blocks beyond one side of the source stage one row / column
     {"win_split", 0, 1, 1},        // window kernel: split blocks and pass windows
-    {"batch_frames", 0, lrp::kMaxBatch, 0}, // frames per wavefront of a batched launch (0: automatic)
+    {"batch_frames", 0, lrp::kMaxBatch, 0}, // frames per wavefront of a batched launch (0: automatic); > 1 on a launch that reads the geometry cache: one block per wavefront, whatever geo_strip says
     {"multi_fork", 0, kMaxSideStreams, 1},    // side streams of lrp_reproject_multi_device
     {"geo_cache", 0, 1, 1},        // geometry cache used by single launches (0: every launch computes)
-    {"geo_strip", 0, lrp::kGeoStripRows, 0}, // blocks per wavefront of a launch that reads the geometry cache (0: automatic)
+    {"geo_strip", 0, lrp::kGeoStripRows, 0}, // blocks per wavefront of a launch that reads the geometry cache (0: automatic); launches without the frame loop only
     {"geo_big", 0, 2, 1},            // big-window variant of the kernels that read the geometry cache (a rectilinear view rendered into a panorama); 0: the four-wavefront instantiation
     {"geo_lists", 0, 2, 1},        // rendering by block class from the lists of a geometry-cache entry (corner runs by the fill kernel / a share per wavefront, the window kernel over the work list): 0 never, 1 where at least 30 % of the blocks are corner blocks, 2 whenever the lists are known
     {"geo_fill_stream", 0, 1, 0}, // the fill kernel of a listed launch: 0 in front of the window kernel on the caller's stream, 1 beside it on a side stream of the device

@@ -17,7 +17,10 @@ template <int CH> constexpr int corner_fill_vectors() { return (kGeoRunBlocks * 
 
 // Row segments [seg_first, seg_end) of the runs (segment s = pixel row s % 16 of run s / 16) of one frame: `src` supplies the
 // corner texels, `dst` receives the rows.  seg_first / seg_end are wave-uniform; all 64 lanes of the wavefront take part.
-template <int CH>
+// Opaque: the channels of the value are selected from opaque copies (RGB / RGBAZ: the chain of selects over the elements of
+// c[] is otherwise turned back into an indexed load, and the array then lives in scratch memory) — the frame-loop GeoRead
+// window kernels, which own no scratch otherwise.
+template <int CH, bool Opaque = false>
 __device__ __forceinline__ void corner_fill_rows(const KParams &P, const float *src, float *dst, uint32_t seg_first, uint32_t seg_end) {
   static_assert(CH == 3 || CH == 4 || CH == 5, "RGB, RGBA or RGBAZ");
   typedef float v4f_a4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -84,6 +87,11 @@ __device__ __forceinline__ void corner_fill_rows(const KParams &P, const float *
           const int m = (4 * lane + 256 * i) % CH;
           auto at = [&](int n) {
             const int j = (m + n) % CH;
+            if constexpr (Opaque) {
+              float c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3], c4 = c[4];
+              asm volatile("" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3), "+v"(c4));
+              return j == 0 ? c0 : j == 1 ? c1 : j == 2 ? c2 : j == 3 ? c3 : c4;
+            }
             float v = c[0];
 #pragma unroll
             for (int t = 1; t < CH; ++t) v = j == t ? c[t] : v;

@@ -161,6 +161,11 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
   KParams P = Pk; // src / dst: the frame being rendered (set_frame below)
   P.src = frame_src(0);
   P.dst = frame_dst(0);
+  // The frame-loop GeoRead instantiations render ONE block per wavefront: the launcher gives every launch that takes them
+  // blocks_per_wave 1 (launch_win_bicubic_impl), and here that is a compile-time fact — no successor block `nxt`, no fetch
+  // or plan of its record, no block loop.  (Carried for a second block that never came, that state cost the headline
+  // instantiation 14 spilled SGPRs, 6 spilled VGPRs and two scratch reloads behind the sample of every pass.)
+  constexpr bool kOneBlock = Frames && GeoRead;
   constexpr bool Loop = (InMode == kInEquirectLoop);
   // Edge blocks (WinBlockT::edge) are compiled for the rectilinear source only: a narrow view inside a wider target is
   // where whole blocks lie beyond one side of the source; in the other instantiations the extra code costs 2-3 % (measured:
@@ -214,7 +219,7 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
       if (per_wave != 0 && blockIdx.x % Pk.geo_fill_stride == 0) {
         const uint32_t total = Pk.geo_n_runs * 16u, s0 = blockIdx.x / Pk.geo_fill_stride * per_wave;
         if (s0 < total)
-          for (int f = 0; f < n_frames; ++f) corner_fill_rows<CH>(Pk, frame_src(f), frame_dst(f), s0, min(s0 + per_wave, total));
+          for (int f = 0; f < n_frames; ++f) corner_fill_rows<CH, kOneBlock>(Pk, frame_src(f), frame_dst(f), s0, min(s0 + per_wave, total));
       }
     }
   };
@@ -287,14 +292,14 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
       ty = g_reverse ? P.tiles_y - 1 - ty : ty;
     }
   }
-  const int lane = (int)(threadIdx.x & 63u);
+  int lane = (int)(threadIdx.x & 63u);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int Gs = P.blocks_per_wave; // blocks per strip of this launch
+  const int Gs = kOneBlock ? 1 : P.blocks_per_wave; // blocks per strip of this launch
   // blocks this strip renders.  (A block wholly below the image re-renders the image's last row — every lane stores — which is
   // how the compute kernels keep their store count.  GeoRead skips such blocks: the entry holds extremes only for the block
   // rows the WRITING launch walked, and that launch may have cut its strips differently.)
-  const int G = GeoRead ? min(Gs, (P.y_end - P.y_offset + kBlockRows - 1) / kBlockRows - ty * Gs) : Gs;
-  auto block_row = [&](int g) { return (kAliasPairs && g_reverse) ? G - 1 - g : g; }; // block of a plain strip rendered by iteration g
+  const int G = kOneBlock ? 1 : GeoRead ? min(Gs, (P.y_end - P.y_offset + kBlockRows - 1) / kBlockRows - ty * Gs) : Gs;
+  auto block_row = [&](int g) { return kOneBlock ? 0 : (kAliasPairs && g_reverse) ? G - 1 - g : g; }; // block of a plain strip rendered by iteration g
   // ... and its class byte (lrp_params.h)
   auto geo_classes = [&]() { return reinterpret_cast<uint8_t *>(P.geo_box) + geo_class_offset(P.out_w, P.out_h); };
   auto geo_class_index = [&](int g) { return (uint32_t)tx * geo_block_rows(P.out_h) + (uint32_t)(ty * Gs + block_row(g)); };
@@ -916,6 +921,14 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
     const int cls0 = geo_class(0);
     if (cls0 == 0) geo_fetch(0, cur);
     geo_plan(cur, cls0, 0);
+    // (one block: its record is planned once and read for every frame — scalar, whatever the selects of the plan left in
+    // vector registers, so that nothing derived from it is a per-lane value to be held across the frame loop)
+    if constexpr (kOneBlock) {
+      auto uniform = [](int &v) { v = __builtin_amdgcn_readfirstlane(v); };
+      for (int *v : {&cur.x_lo, &cur.y_lo, &cur.bw, &cur.bh, &cur.pitch, &cur.tier, &cur.iy0[0], &cur.iy0[1], &cur.iyn[0], &cur.iyn[1],
+                     &cur.c_plane, &cur.c_base, &cur.tap_base})
+        uniform(*v);
+    }
   } else {
     coords(0, cur);
   }
@@ -924,18 +937,18 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
   bool dma_early = false; // the pending window was requested before its block's last store
   // The step after (block g_loop, frame f_loop): the same block in the next frame, or the next block in the first frame.
   auto issue_next = [&]() {
-    if (f_loop + 1 < n_frames)
+    if (kOneBlock || f_loop + 1 < n_frames)
       issue(frame_src(f_loop + 1), cur);
     else
       issue(frame_src(0), nxt);
   };
-  auto has_next = [&]() { return f_loop + 1 < n_frames || g_loop + 1 < G; };
+  auto has_next = [&]() { return f_loop + 1 < n_frames || (!kOneBlock && g_loop + 1 < G); };
   auto next_window = [&]() {
     // while this block's coefficient planes are still being read the next raw window must stay in front of them
     // (the same block's window in the next frame always does: planes sit behind the raw window)
     // (likewise the plane of vertical cubics of a block beyond the first / last source row: edge() 1, 2)
     const bool planes_live = (kCoefHere && cur.coef()) || (kEdge && cur.edge() != 0 && cur.edge() < 3);
-    dma_early = has_next() && (!planes_live || f_loop + 1 < n_frames || raw_slots(nxt) <= cur.c_base);
+    dma_early = has_next() && (kOneBlock || !planes_live || f_loop + 1 < n_frames || raw_slots(nxt) <= cur.c_base);
     if (dma_early) issue_next();
   };
   // The result of pass k of block g: num_samples == 1, (0.0f + s) * normalize (src/reproject.cpp:334-341), store.
@@ -1226,10 +1239,14 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
    // (GeoRead: the next block's record is requested behind this block's wait and planned in front of its last pass — the
    // loads are then older than the next window's DMA and the hand-counted vmcnt(1) below still holds)
    if constexpr (!GeoRead)
-     if ((!Quad || kSharedRays) && g + 1 < G) coords(g + 1, nxt); // (shared rays: the rotation and the source lens run per image, as for a plain block)
+     if ((!Quad || kSharedRays) && !kOneBlock && g + 1 < G) coords(g + 1, nxt); // (shared rays: the rotation and the source lens run per image, as for a plain block)
 #pragma unroll 1
    for (int f = 0; f < n_frames; ++f) {
     f_loop = f;
+    // (one block: everything derived from the block record is the same in every frame, and what is per lane of it — LDS
+    // addresses of the planes, DMA offsets, masks — gets hoisted out of the frame loop into registers the passes need: opaque,
+    // those few adds and shifts run per frame)
+    if constexpr (kOneBlock) asm volatile("" : "+v"(lane));
     if (n_frames > 1 || g == 0) set_frame(f);
     const bool last_frame = f + 1 == n_frames; // the next step is the next block
     // (a launch that writes the geometry cache has the stores of coords(g + 1) in flight as well: it waits for everything)
@@ -1240,7 +1257,7 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
     else
       asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); // window g has landed; block g-1's last store may be in flight
     if constexpr (GeoRead)
-      if (g + 1 < G && f == 0 && geo_class(g + 1) == 0) geo_fetch(g + 1, nxt);
+      if (!kOneBlock && g + 1 < G && f == 0 && geo_class(g + 1) == 0) geo_fetch(g + 1, nxt);
     const float4 *const win = win0;
     // The tier of this block in a scalar register for the branches below: carried through the block loop inside `cur` it
     // ends up in a VGPR (the kernel is at the SGPR limit), and every test of it then costs a v_and + v_cmp and the
@@ -1256,12 +1273,12 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
       // every pixel of this block is one value: no taps, no per-pixel arithmetic — four stores.  The next block's
       // window is requested in front of the last store, as in the last pass of an ordinary block.
       const Rgba cs = corner_value(cur);
-      if (Quad && !kSharedRays && last_frame && g + 1 < G) coords(g + 1, nxt);
+      if (Quad && !kSharedRays && last_frame && !kOneBlock && g + 1 < G) coords(g + 1, nxt);
       if constexpr (GeoRead)
-        if (g + 1 < G && last_frame) geo_plan(nxt, geo_class(g + 1), g + 1);
+        if (!kOneBlock && g + 1 < G && last_frame) geo_plan(nxt, geo_class(g + 1), g + 1);
       emit_corner(g, cs, [&]() { next_window(); });
       if (!dma_early && has_next()) issue_next();
-      if (last_frame) cur = nxt;
+      if (!kOneBlock && last_frame) cur = nxt;
       continue;
     }
     // The big-window variant: a block with nothing staged — its four passes take a window of their own, tap DMA or gathers,
@@ -1285,7 +1302,7 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
         bool behind_store = true; // what this pass reads was requested behind the previous pass's store: nothing younger in flight
 #pragma unroll 1
         for (int k = 0; k < 4; ++k) {
-          if (k == 3 && g + 1 < G && last_frame) geo_plan(nxt, geo_class(g + 1), g + 1);
+          if (k == 3 && !kOneBlock && g + 1 < G && last_frame) geo_plan(nxt, geo_class(g + 1), g + 1);
           const float psx = pass_x(k), psy = pass_y(k);
           if constexpr (!kPipeline) { // planned, requested, waited for and read on the spot
             const bool last_pass = k == 3;
@@ -1359,7 +1376,7 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
           }
         }
         if (!dma_early && has_next()) issue_next();
-        if (last_frame) cur = nxt;
+        if (!kOneBlock && last_frame) cur = nxt;
         continue;
       }
     }
@@ -1374,9 +1391,9 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
 #pragma unroll(kBigWin && CH == 5 ? 1 : 2)
       for (int kk = 0; kk < 2; ++kk) {
         const int k = 2 * h + kk;
-        if (Quad && !kSharedRays && k == 3 && last_frame && g + 1 < G) coords(g + 1, nxt); // only its box is kept
+        if (Quad && !kSharedRays && k == 3 && last_frame && !kOneBlock && g + 1 < G) coords(g + 1, nxt); // only its box is kept
         if constexpr (GeoRead)
-          if (k == 3 && g + 1 < G && last_frame) geo_plan(nxt, geo_class(g + 1), g + 1);
+          if (k == 3 && !kOneBlock && g + 1 < G && last_frame) geo_plan(nxt, geo_class(g + 1), g + 1);
         const bool last_pass = k == 3;
         float psx = kk == 0 ? hx0 : hx1, psy = kk == 0 ? hy0 : hy1;
         if constexpr (Quad && !kSharedRays) quad_xy(image_of(g), k, psx, psy); // re-derived (2-4 instructions) instead of held in registers
@@ -1443,7 +1460,7 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
       }
     }
     if (!dma_early && has_next()) issue_next(); // after the last read of the planes
-    if (last_frame) cur = nxt;
+    if (!kOneBlock && last_frame) cur = nxt;
    }
   }
   fill_share();
@@ -1550,7 +1567,7 @@ inline hipError_t launch_win_bicubic_impl(KParams P, int out_lens, int in_mode, 
     P.blocks_per_wave = G;
     P.tiles_y = (row_blocks + G - 1) / G;
   }
-  const int n_tiles = P.tiles_x * P.tiles_y;
+  int n_tiles = P.tiles_x * P.tiles_y;
   if (n_tiles <= 0) return hipSuccess;
   // Frames per wavefront of a batched launch: as many as leave at least two rounds of wavefronts on the chip
   // (4096 wave slots), so that a 4K batch of 16 runs every strip through all 16 frames and small images keep the chip full.
@@ -1569,6 +1586,13 @@ inline hipError_t launch_win_bicubic_impl(KParams P, int out_lens, int in_mode, 
     if (SS) F = 1;
     P.frames_per_wave = F;
     if (F > 1 && !win_kernel<QMode, CH, GeoRead, SS, Set>(P, out_lens, in_mode)) P.frames_per_wave = F = 1; // no frame loop for this cell: a frame per workgroup row
+    // the frame-loop GeoRead kernels render one block per wavefront (kOneBlock): a longer strip reaches this point only when
+    // "batch_frames" forces the frame loop on the one mapping that keeps its strips in a batch (rectilinear -> equirect)
+    if (GeoRead && F > 1 && P.blocks_per_wave != 1) {
+      P.blocks_per_wave = 1;
+      P.tiles_y = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
+      n_tiles = P.tiles_x * P.tiles_y;
+    }
     groups = (P.batch_n + F - 1) / F;
   }
   const TileKernelFn fn = win_kernel<QMode, CH, GeoRead, SS, Set>(P, out_lens, in_mode);
