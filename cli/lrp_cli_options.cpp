@@ -35,14 +35,17 @@ const Option kOptions[] = {
     {"output-resolution", 0, true, nullptr, "width,height", "Fixed output resolution; overrides --scale.", "Sampling"},
     {"i-rectilinear", 0, true, nullptr, "focal_length,sensor_width", "Input images are rectilinear.", "Input optics (with --no-configs)"},
     {"i-equisolid", 0, true, nullptr, "focal_length,sensor_width,fov", "Input images are equisolid fisheye (rendered with --allow-equisolid; rejected by reproject() otherwise, as in the reference).", "Input optics (with --no-configs)"},
+    {"i-stereographic", 0, true, nullptr, "focal_length,sensor_width", "Input images are stereographic fisheye (rendered with --allow-stereographic; rejected by reproject() otherwise, as in the reference).", "Input optics (with --no-configs)"},
     {"i-equidistant", 0, true, nullptr, "fov", "Input images are equidistant fisheye.", "Input optics (with --no-configs)"},
     {"i-equirectangular", 0, true, nullptr, "long_min,long_max,lat_min,lat_max | full", "Input images are equirectangular (radians).", "Input optics (with --no-configs)"},
     {"no-reproject", 0, false, nullptr, "", "Keep the input lens (scaling / colour processing only).", "Output optics"},
     {"rectilinear", 0, true, nullptr, "focal_length,sensor_width", "Output rectilinear images.", "Output optics"},
     {"equisolid", 0, true, nullptr, "focal_length,sensor_width,fov", "Output equisolid images (rendered with --allow-equisolid; rejected by reproject() otherwise, as in the reference).", "Output optics"},
+    {"stereographic", 0, true, nullptr, "focal_length,sensor_width", "Output stereographic images (rendered with --allow-stereographic; rejected by reproject() otherwise, as in the reference).", "Output optics"},
     {"equidistant", 0, true, nullptr, "fov", "Output equidistant fisheye images.", "Output optics"},
     {"equirectangular", 0, true, nullptr, "long_min,long_max,lat_min,lat_max | full", "Output equirectangular images.", "Output optics"},
     {"allow-equisolid", 0, false, nullptr, "", "Render equisolid fisheye lenses (--equisolid, --i-equisolid, FISHEYE_EQUISOLID configs; r = 2 f sin(theta / 2)): an extension, the reference rejects them.", "Output optics"},
+    {"allow-stereographic", 0, false, nullptr, "", "Render stereographic fisheye lenses (--stereographic, --i-stereographic, FISHEYE_STEREOGRAPHIC configs; r = 2 f tan(theta / 2), the little-planet projection): an extension, the reference rejects them.", "Output optics"},
     {"rotation", 0, true, "0.0", "pan,pitch,roll (degrees)", "Rotate the view.", "Output optics"},
     {"exposure", 0, true, "0.0", "EV", "Exposure compensation in stops.", "Color processing"},
     {"reinhard", 0, true, "1.0", "max", "Reinhard tone mapping with this maximum (after exposure).", "Color processing"},

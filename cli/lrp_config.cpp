@@ -30,11 +30,13 @@ struct Model {
 };
 
 // u.rectilinear {focal_length}; u.fisheye_equidistant {fov}; u.fisheye_equisolid {focal_length, fov};
+// u.fisheye_stereographic {focal_length} (this project's extension: the reference's config code does not know the type);
 // u.equirectangular {latitude_min, latitude_max, longitude_min, longitude_max}
 const Model kModels[] = {
     {LRP_RECTILINEAR, "PERSP", nullptr, nullptr, {{"focal_length", 0}}, 1},
     {LRP_FISHEYE_EQUIDISTANT, "PANO", "FISHEYE_EQUIDISTANT", "FISHEYE_EQUIDISTANT", {{"fisheye_fov", 0}}, 1},
     {LRP_FISHEYE_EQUISOLID, "PANO", "FISHEYE_EQUISOLID", "FISHEYE_EQUISOLID", {{"fisheye_lens", 0}, {"fisheye_fov", 1}}, 2},
+    {LRP_FISHEYE_STEREOGRAPHIC, "PANO", "FISHEYE_STEREOGRAPHIC", "FISHEYE_STEREOGRAPHIC", {{"fisheye_lens", 0}}, 1},
     {LRP_EQUIRECTANGULAR, "PANO", "EQUIRECTANGULAR", "RECTILINEAR" /* (sic) */,
      {{"latitude_min", 0}, {"latitude_max", 1}, {"longitude_min", 2}, {"longitude_max", 3}}, 4},
 };

@@ -64,6 +64,16 @@ bool lens_equisolid(const std::string &text, float res_x, float res_y, lrp_lens 
   return true;
 }
 
+bool lens_stereographic(const std::string &text, float res_x, float res_y, lrp_lens &lens) {
+  const std::vector<std::string> v = split(text, ',');
+  if (v.size() < 2) {
+    std::printf("Error: Required format for --stereographic focal_len,sensor_width\n");
+    return false;
+  }
+  lrp_lens_stereographic(&lens, number(v[0]), number(v[1]), res_x, res_y);
+  return true;
+}
+
 bool lens_equidistant(const std::string &text, float, float, lrp_lens &lens) {
   lrp_lens_equidistant(&lens, number(text));
   return true;
@@ -86,6 +96,7 @@ bool lens_equirectangular(const std::string &text, float, float, lrp_lens &lens)
 
 const LensFlag kLensFlags[] = {{"rectilinear", lens_rectilinear},
                                {"equisolid", lens_equisolid},
+                               {"stereographic", lens_stereographic},
                                {"equidistant", lens_equidistant},
                                {"equirectangular", lens_equirectangular}};
 
@@ -186,7 +197,7 @@ int resolve_input_lens(const CommandLine &cl, const char *argv0, RunPlan &p) {
     const int found = apply_lens_flags(cl, "i-", (float)p.in_width, (float)p.in_height, p.input_lens);
     if (found < 0) return 1;
     if (found > 1) {
-      std::printf("Error: only specify one input lens type: [--i-rectilinear, --i-equisolid, --i-equidistant, "
+      std::printf("Error: only specify one input lens type: [--i-rectilinear, --i-equisolid, --i-stereographic, --i-equidistant, "
                   "--i-equirectangular].\n");
       return 1;
     }
@@ -228,7 +239,7 @@ int resolve_output_lens(const CommandLine &cl, RunPlan &p) {
     ++found;
   }
   if (found > 1) {
-    std::printf("Error: only specify one output lens type: [--rectilinear, --equisolid, --equidistant, "
+    std::printf("Error: only specify one output lens type: [--rectilinear, --equisolid, --stereographic, --equidistant, "
                 "--equirectangular, --no-reproject].\n");
     return 1;
   }

@@ -32,7 +32,8 @@ int main(int argc, char **argv) {
     std::printf("%s\n", help_text(argv[0]).c_str());
     return 0;
   }
-  if (cl.has("allow-equisolid")) lrp_lens_extensions(LRP_LENS_EXT_EQUISOLID); // the opt-in lens extension (include/lrp.h)
+  // the opt-in lens extensions (include/lrp.h)
+  lrp_lens_extensions((cl.has("allow-equisolid") ? LRP_LENS_EXT_EQUISOLID : 0) | (cl.has("allow-stereographic") ? LRP_LENS_EXT_STEREOGRAPHIC : 0));
   RunPlan plan;
   if (int rc = resolve_run_plan(cl, argv[0], plan)) return rc;
 

@@ -113,6 +113,14 @@ class LensInfo:
         return cls._from_c(c)
 
     @classmethod
+    def stereographic(cls, focal_length, sensor_width, res_x, res_y):
+        """--stereographic focal_len,sensor_width: r = 2 f tan(theta / 2) (include/lrp.h); sensor_height = res_y / res_x *
+        sensor_width.  Renders only while the LENS_EXT_STEREOGRAPHIC extension is on (lens_extensions)."""
+        c = LrpLens()
+        _native.load().lrp_lens_stereographic(ctypes.byref(c), focal_length, sensor_width, res_x, res_y)
+        return cls._from_c(c)
+
+    @classmethod
     def equirectangular(cls, longitude_min=None, longitude_max=None, latitude_min=None, latitude_max=None):
         """--equirectangular full | lon_min,lon_max,lat_min,lat_max (src/main.cpp:58-95)."""
         c = LrpLens()
@@ -215,6 +223,7 @@ def debug_kernel(choice=-1):
 
 
 LENS_EXT_EQUISOLID = 1  # include/lrp.h LRP_LENS_EXT_EQUISOLID
+LENS_EXT_STEREOGRAPHIC = 0x100  # include/lrp.h LRP_LENS_EXT_STEREOGRAPHIC
 
 
 def lens_extensions(mask=None):

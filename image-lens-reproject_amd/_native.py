@@ -157,6 +157,10 @@ SYMBOLS = {
         None,
         [_P(LrpLens), ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float],
     ),
+    "lrp_lens_stereographic": (
+        None,
+        [_P(LrpLens), ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float],
+    ),
     "lrp_lens_extensions": (ctypes.c_int, [ctypes.c_int]),
     "lrp_lens_equirectangular": (
         None,

@@ -1,7 +1,7 @@
 // lrp_capi.cpp — the C ABI declared in include/lrp.h: argument validation in the
 // reference's dispatch order, kernel-argument construction, device buffers,
 // streams and the batch context.  Host code only; the kernels live in the
-// lrp_kernels_*.hip / lrp_tile_*.hip / lrp_eqs_*.hip (reprojection), lrp_tables.hip, lrp_geo_lists.hip,
+// lrp_kernels_*.hip / lrp_tile_*.hip / lrp_eqs_*.hip / lrp_stg_*.hip (reprojection), lrp_tables.hip, lrp_geo_lists.hip,
 // lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
 #include <hip/hip_runtime.h>
 
@@ -97,7 +97,8 @@ std::atomic<int> g_lens_ext{0};
 // `ext`: the extension mask, read once per call
 bool lens_in_hot_path(int type, int ext) {
   return type == LRP_RECTILINEAR || type == LRP_FISHEYE_EQUIDISTANT || type == LRP_EQUIRECTANGULAR ||
-         (type == LRP_FISHEYE_EQUISOLID && (ext & LRP_LENS_EXT_EQUISOLID) != 0);
+         (type == LRP_FISHEYE_EQUISOLID && (ext & LRP_LENS_EXT_EQUISOLID) != 0) ||
+         (type == LRP_FISHEYE_STEREOGRAPHIC && (ext & LRP_LENS_EXT_STEREOGRAPHIC) != 0);
 }
 
 // LoopHorizontally decision, reference src/reproject.cpp:386-394: float span,
@@ -111,6 +112,7 @@ int in_lens_mode(const lrp_lens &L) {
   if (L.type == LRP_RECTILINEAR) return lrp::kInRect;
   if (L.type == LRP_FISHEYE_EQUIDISTANT) return lrp::kInEquidistant;
   if (L.type == LRP_FISHEYE_EQUISOLID) return lrp::kInEquisolid;
+  if (L.type == LRP_FISHEYE_STEREOGRAPHIC) return lrp::kInStereographic;
   return source_wraps(L) ? lrp::kInEquirectLoop : lrp::kInEquirect;
 }
 
@@ -185,6 +187,9 @@ lrp::KParams make_params(const lrp_image *in, const lrp_image *out, int num_samp
   // equisolid: 2.0f * focal_length, exact (r = 2 f sin(theta / 2), include/lrp.h)
   if (in->lens.type == LRP_FISHEYE_EQUISOLID) P.in_focal = 2.0f * in->lens.u.fisheye_equisolid.focal_length;
   if (out->lens.type == LRP_FISHEYE_EQUISOLID) P.out_focal = 2.0f * out->lens.u.fisheye_equisolid.focal_length;
+  // stereographic: likewise (r = 2 f tan(theta / 2))
+  if (in->lens.type == LRP_FISHEYE_STEREOGRAPHIC) P.in_focal = 2.0f * in->lens.u.fisheye_stereographic.focal_length;
+  if (out->lens.type == LRP_FISHEYE_STEREOGRAPHIC) P.out_focal = 2.0f * out->lens.u.fisheye_stereographic.focal_length;
   P.in_lon_span = in->lens.u.equirectangular.longitude_max - in->lens.u.equirectangular.longitude_min;
   P.in_lat_span = in->lens.u.equirectangular.latitude_max - in->lens.u.equirectangular.latitude_min;
   return P;
@@ -314,14 +319,14 @@ lrp::PlanRequest plan_request(const lrp_image *in, const lrp_image *out, int num
   return r;
 }
 static_assert((int)lrp::kPlanRect == (int)lrp::kRect && (int)lrp::kPlanEquidistant == (int)lrp::kEquidistant && (int)lrp::kPlanEquirect == (int)lrp::kEquirect &&
-                  (int)lrp::kPlanEquisolid == (int)lrp::kEquisolid,
+                  (int)lrp::kPlanEquisolid == (int)lrp::kEquisolid && (int)lrp::kPlanStereographic == (int)lrp::kStereographic,
               "lrp_plan.h numbers lenses like lrp_params.h");
 static_assert((int)lrp::kRect == LRP_RECTILINEAR && (int)lrp::kEquidistant == LRP_FISHEYE_EQUIDISTANT && (int)lrp::kEquisolid == LRP_FISHEYE_EQUISOLID &&
-                  (int)lrp::kEquirect == LRP_EQUIRECTANGULAR,
+                  (int)lrp::kStereographic == LRP_FISHEYE_STEREOGRAPHIC && (int)lrp::kEquirect == LRP_EQUIRECTANGULAR,
               "lrp_params.h numbers lenses like include/lrp.h");
 static_assert((int)lrp::kPlanInRect == (int)lrp::kInRect && (int)lrp::kPlanInEquidistant == (int)lrp::kInEquidistant &&
                   (int)lrp::kPlanInEquirect == (int)lrp::kInEquirect && (int)lrp::kPlanInEquirectLoop == (int)lrp::kInEquirectLoop &&
-                  (int)lrp::kPlanInEquisolid == (int)lrp::kInEquisolid,
+                  (int)lrp::kPlanInEquisolid == (int)lrp::kInEquisolid && (int)lrp::kPlanInStereographic == (int)lrp::kInStereographic,
               "lrp_plan.h numbers input modes like lrp_params.h");
 static_assert((int)lrp::kPlanNearest == LRP_NEAREST && (int)lrp::kPlanBilinear == LRP_BILINEAR && (int)lrp::kPlanBicubic == LRP_BICUBIC, "interpolation numbering");
 
@@ -462,7 +467,7 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
       // census of its windows are built behind it, and their header follows the records to the host (page-locked; read once
       // the records' event has completed)
       const uint8_t *const header = reinterpret_cast<const uint8_t *>(geo.box) + lrp::geo_lists_offset(out->width, out->height);
-      const bool with_lists = im == lrp::kInRect && knob(kKnobGeoLists) != 0, with_census = knob(kKnobGeoCensus) != 0 && im != lrp::kInEquidistant && im != lrp::kInEquisolid;
+      const bool with_lists = im == lrp::kInRect && knob(kKnobGeoLists) != 0, with_census = knob(kKnobGeoCensus) != 0 && !lrp::radial_in(im);
       if (!with_lists && !with_census) {
         // (nothing to tell the host about this entry)
       } else if ((!with_lists || lrp::launch_geo_build_lists(geo.box, out->width, out->height, P.alias_pairs, stream) == hipSuccess) &&
@@ -568,7 +573,7 @@ int lrp_abi_version(void) { return LRP_ABI_VERSION; }
 
 int lrp_lens_extensions(int mask) {
   if (mask < 0) return g_lens_ext.load(std::memory_order_relaxed);
-  return g_lens_ext.exchange(mask & LRP_LENS_EXT_EQUISOLID, std::memory_order_relaxed);
+  return g_lens_ext.exchange(mask & (LRP_LENS_EXT_EQUISOLID | LRP_LENS_EXT_STEREOGRAPHIC), std::memory_order_relaxed);
 }
 
 int lrp_debug_kernel(int choice) {

@@ -103,6 +103,17 @@ __device__ __forceinline__ void target_ray(const LensP &L, float img_w, float im
     vx = s * cx;
     vy = s * cy;
     vz = cs;
+  } else if constexpr (OutLens == kStereographic) {
+    // stereographic_to_vec (include/lrp.h: r = 2 f tan(theta / 2), no libm call); p[0] = focal_length
+    const float r_px = lrp_sqrtf(cx * cx + cy * cy);
+    const float r_mm = r_px / img_w * L.sensor_width;
+    const float t = r_mm / (2.0f * L.p[0]);
+    const float t2 = t * t;
+    const float d = 1.0f + t2;
+    const float s = ((2.0f * t) / d) / r_px;
+    vx = s * cx;
+    vy = s * cy;
+    vz = (1.0f - t2) / d;
   } else {
     // equirectangular_to_vec, src/reproject.cpp:245-257
     const float lat_min = L.p[0], lat_max = L.p[1], lon_min = L.p[2], lon_max = L.p[3];
@@ -149,6 +160,16 @@ __device__ __forceinline__ void ray_to_source(const LensP &L, float img_w, float
     const float r = lrp_sqrtf(x * x + y * y);
     const float theta = atanf_(r);
     const float r_mm = (2.0f * L.p[0]) * sinf_(0.5f * theta);
+    const float r_px = r_mm / L.sensor_width * img_w;
+    cx = x / r * r_px;
+    cy = y / r * r_px;
+  } else if constexpr (InMode == kInStereographic) {
+    // vec_to_stereographic (include/lrp.h); p[0] = focal_length
+    x = x / -z;
+    y = y / -z;
+    const float r = lrp_sqrtf(x * x + y * y);
+    const float t = r / (1.0f + lrp_sqrtf(1.0f + r * r));
+    const float r_mm = (2.0f * L.p[0]) * t;
     const float r_px = r_mm / L.sensor_width * img_w;
     cx = x / r * r_px;
     cy = y / r * r_px;

@@ -39,7 +39,8 @@ namespace lrp {
 LensP geo_canonical_lens(const LensP &lens, int lens_type) {
   LensP c = lens;
   // include/lrp.h lrp_lens (reference src/config.hpp:15-37): rectilinear {focal_length}, equidistant {fov},
-  // equirectangular {latitude_min, latitude_max, longitude_min, longitude_max}
+  // equirectangular {latitude_min, latitude_max, longitude_min, longitude_max}; the extensions: equisolid {focal_length, fov},
+  // stereographic {focal_length}
   const int used = lens_type == LRP_EQUIRECTANGULAR ? 4 : (lens_type == LRP_FISHEYE_EQUISOLID ? 2 : 1);
   for (int i = used; i < 4; ++i) c.p[i] = 0.0f;
   return c;

@@ -57,6 +57,14 @@ void lrp_lens_equisolid(lrp_lens *lens, float focal_length, float sensor_width, 
   lens->sensor_height = res_y / res_x * sensor_width; // the CLI's convention, src/main.cpp:45
 }
 
+void lrp_lens_stereographic(lrp_lens *lens, float focal_length, float sensor_width, float res_x, float res_y) {
+  std::memset(lens, 0, sizeof(*lens));
+  lens->type = LRP_FISHEYE_STEREOGRAPHIC;
+  lens->u.fisheye_stereographic.focal_length = focal_length;
+  lens->sensor_width = sensor_width;
+  lens->sensor_height = res_y / res_x * sensor_width; // as the equisolid lens
+}
+
 void lrp_lens_equirectangular(lrp_lens *lens, float longitude_min, float longitude_max, float latitude_min,
                               float latitude_max) {
   std::memset(lens, 0, sizeof(*lens));

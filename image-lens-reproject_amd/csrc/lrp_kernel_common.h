@@ -133,6 +133,14 @@ __device__ __forceinline__ void ray_to_source_v2(const KParams &P, float x, floa
     const float r_px = r_mm / L.sensor_width * img_w;
     cx = x / r * r_px;
     cy = y / r * r_px;
+  } else if constexpr (InMode == kInStereographic) {
+    // vec_to_stereographic (include/lrp.h): r_mm = 2 f tan(theta / 2) without a libm call, P.in_focal = 2.0f * focal_length (exact)
+    const float r = lrp_sqrtf(x * x + y * y);
+    const float t = r / (1.0f + lrp_sqrtf(1.0f + r * r));
+    const float r_mm = P.in_focal * t;
+    const float r_px = r_mm / L.sensor_width * img_w;
+    cx = x / r * r_px;
+    cy = y / r * r_px;
   } else {
     const float lat_min = L.p[0], lon_min = L.p[2];
     cx = equirect_cx(x, z, lon_min, P.in_lon_span, img_w);    // :262, :268
@@ -165,6 +173,19 @@ __device__ __forceinline__ void equisolid_ray_v2(const KParams &P, float cx, flo
   vx = s * cx;
   vy = s * cy;
   vz = cs;
+}
+
+// stereographic_to_vec (include/lrp.h) with 2.0f * focal_length hoisted into P.out_focal (exact): no libm call.
+__device__ __forceinline__ void stereographic_ray_v2(const KParams &P, float cx, float cy, float &vx, float &vy, float &vz) {
+  const float r_px = lrp_sqrtf(cx * cx + cy * cy);
+  const float r_mm = r_px / (float)P.out_w * P.out_lens.sensor_width;
+  const float t = r_mm / P.out_focal;
+  const float t2 = t * t;
+  const float d = 1.0f + t2;
+  const float s = ((2.0f * t) / d) / r_px;
+  vx = s * cx;
+  vy = s * cy;
+  vz = (1.0f - t2) / d;
 }
 
 // The reference's tap indices (src/reproject.cpp:114-127).
@@ -408,6 +429,8 @@ __device__ __forceinline__ void pixel_ray(const KParams &P, const ColTerms col, 
     const float scy = cy + ((float)ssy + 1.0f) / ((float)P.num_samples + 1.0f) - 0.5f; // :298
     if constexpr (OutLens == kEquisolid)
       equisolid_ray_v2(P, col.a, scy, vx, vy, vz);
+    else if constexpr (OutLens == kStereographic)
+      stereographic_ray_v2(P, col.a, scy, vx, vy, vz);
     else
       equidistant_ray_v2(P, col.a, scy, vx, vy, vz);
   }

@@ -8,14 +8,14 @@
 namespace lrp {
 
 // Lens model ids used as template arguments (numbering of include/lrp.h /
-// reference src/config.hpp:7-13).  kEquisolid: the opt-in lens extension (lrp_lens_extensions).
-enum : int { kRect = 0, kEquidistant = 1, kEquisolid = 2, kEquirect = 4 };
+// reference src/config.hpp:7-13).  kEquisolid, kStereographic: the opt-in lens extensions (lrp_lens_extensions).
+enum : int { kRect = 0, kEquidistant = 1, kEquisolid = 2, kStereographic = 3, kEquirect = 4 };
 // Input-lens mode: equirectangular sources split into clamped and wrapping
-// (reference LoopHorizontally, src/reproject.cpp:386-394); kInEquisolid: the extension's source.
-enum : int { kInRect = 0, kInEquidistant = 1, kInEquirect = 2, kInEquirectLoop = 3, kInEquisolid = 4 };
+// (reference LoopHorizontally, src/reproject.cpp:386-394); kInEquisolid, kInStereographic: the extensions' sources.
+enum : int { kInRect = 0, kInEquidistant = 1, kInEquirect = 2, kInEquirectLoop = 3, kInEquisolid = 4, kInStereographic = 5 };
 // The fisheye lenses: radially symmetric, no separable output-lens terms, no column-separable source x.
-constexpr bool radial_out(int lens) { return lens == kEquidistant || lens == kEquisolid; }
-constexpr bool radial_in(int mode) { return mode == kInEquidistant || mode == kInEquisolid; }
+constexpr bool radial_out(int lens) { return lens == kEquidistant || lens == kEquisolid || lens == kStereographic; }
+constexpr bool radial_in(int mode) { return mode == kInEquidistant || mode == kInEquisolid || mode == kInStereographic; }
 constexpr int kMaxBatch = 16; // frames of one geometry rendered by one launch (blockIdx.y = frame)
 constexpr int kXcds = 8; // XCDs (private L2s) of an MI355X; blockIdx % 8 labels the blocks that share one
 // XCD-aware tile numbering.  The dispatcher deals workgroup i to XCD i % 8.  The rows of tiles are cut
@@ -77,7 +77,7 @@ struct KParams {
   const float *xsep_tab; // [3][out_w * num_samples]
   // Lens constants that depend on the lens only, evaluated once on the host
   // with the same IEEE binary32 operations (src/reproject.cpp:178,196,251-252,265-266).
-  float in_focal, out_focal;        // equidistant: sensor_width / fov; equisolid: 2.0f * focal_length (exact)
+  float in_focal, out_focal;        // equidistant: sensor_width / fov; equisolid, stereographic: 2.0f * focal_length (exact)
   float in_lon_span, in_lat_span;   // equirectangular source
   int32_t blocks_per_wave;          // window kernel: 16 x 16 blocks per wavefront strip
   int32_t win_coef;                 // window kernel: shared tap-column coefficients allowed (0: raw taps only)

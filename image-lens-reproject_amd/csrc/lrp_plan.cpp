@@ -7,6 +7,10 @@
 
 namespace lrp {
 
+// The fisheye lenses of the opt-in extensions (equisolid, stereographic): treated like the equidistant lens, less every sharing path.
+static bool ext_out(int out_type) { return out_type == kPlanEquisolid || out_type == kPlanStereographic; }
+static bool ext_in(int in_mode) { return in_mode == kPlanInEquisolid || in_mode == kPlanInStereographic; }
+
 PlanFamily plan_family(const PlanRequest &r, const PlanSwitches &s) {
   PlanFamily f;
   // The tile / window kernels are instantiated for RGB, RGBA and RGBAZ (what the reference's codecs deliver,
@@ -15,7 +19,7 @@ PlanFamily plan_family(const PlanRequest &r, const PlanSwitches &s) {
   f.tile = s.kernel != 0 && tile_channels && r.byte_offsets_fit && r.in_w <= 65535 && r.in_h <= 32767 &&
            (long long)r.out_w * r.num_samples < (1ll << 30) && (long long)r.out_h * r.num_samples < (1ll << 30);
   // separable output-lens terms: the rectilinear and the equirectangular target (the fisheye ones are not separable)
-  f.wants_tables = f.tile && r.out_type != kPlanEquidistant && r.out_type != kPlanEquisolid;
+  f.wants_tables = f.tile && r.out_type != kPlanEquidistant && !ext_out(r.out_type);
   return f;
 }
 
@@ -29,7 +33,7 @@ PlanRotation plan_rotation(const PlanRequest &r, const PlanSwitches &s, const Pl
   if (p.has_rot && std::memcmp(r.rot, kIdentity, sizeof(kIdentity)) == 0) p.has_rot = false;
   // Column-separable source x (lrp_tables.hip): ray x and z independent of the row.
   const bool rows_free = !p.has_rot || (r.rot[1] == 0.0f && r.rot[7] == 0.0f);
-  p.wants_xsep = s.xsep != 0 && rows_free && r.in_mode != kPlanInEquidistant && r.in_mode != kPlanInEquisolid;
+  p.wants_xsep = s.xsep != 0 && rows_free && r.in_mode != kPlanInEquidistant && !ext_in(r.in_mode);
   return p;
 }
 
@@ -39,8 +43,8 @@ PlanSharing plan_sharing(const PlanRequest &r, const PlanSwitches &s, const Plan
   if (!f.tile) return p;
   const int symmetry = (f.wants_tables && t.built) ? t.symmetry : 0;
   const bool out_eqd = r.out_type == kPlanEquidistant;
-  // The equisolid lens (either side) renders plain pixels and blocks only: no mirrored pixels, blocks or rays.
-  const bool eqs = r.out_type == kPlanEquisolid || r.in_mode == kPlanInEquisolid;
+  // An extension fisheye (either side) renders plain pixels and blocks only: no mirrored pixels, blocks or rays.
+  const bool ext = ext_out(r.out_type) || ext_in(r.in_mode);
   const int ns = r.num_samples, interp = r.interpolation, k = s.kernel;
   // Mirrored pixels / blocks: without a rotation the mapping is symmetric about both image axes and the lens-plane
   // coordinates of the four mirror pixels differ in sign only.  Rectilinear / equirectangular target: the ray tables must be
@@ -50,7 +54,7 @@ PlanSharing plan_sharing(const PlanRequest &r, const PlanSwitches &s, const Plan
   const bool in_eqr = r.in_mode == kPlanInEquirect || r.in_mode == kPlanInEquirectLoop;
   const bool sym_out = out_eqd ? true : symmetry == 3;
   const bool sharing = s.quad != 0 && k != 3;
-  p.quad = (!r.band && sharing && !eqs && ns == 1 && !rot.has_rot && sym_out && (!in_eqr || xsep_available)) ? 1 : 0;
+  p.quad = (!r.band && sharing && !ext && ns == 1 && !rot.has_rot && sym_out && (!in_eqr || xsep_available)) ? 1 : 0;
   // A batch of nearest-neighbour frames shares its coordinates between up to 16 frames (the plain path of the tile
   // kernel keeps them in registers), which beats sharing them between four mirror pixels: 71 -> 66 us per 4K frame.
   // ... and likewise for bilinear (same-box A/B, 16-frame launches: equirect -> rect 91.7 -> 83.7 us, fisheye -> rect 90.9 ->
@@ -64,7 +68,7 @@ PlanSharing plan_sharing(const PlanRequest &r, const PlanSwitches &s, const Plan
   p.window1 = p.window && ns == 1;
   // Equidistant target, rotated (or an equirectangular source): the four mirror pixels still share the ray through the
   // output lens (tile kernels only).
-  if (!r.band && p.quad == 0 && !p.window && !batch_plain && sharing && !eqs && ns == 1 && out_eqd) p.quad = 2;
+  if (!r.band && p.quad == 0 && !p.window && !batch_plain && sharing && !ext && ns == 1 && out_eqd) p.quad = 2;
   p.win_coef = k == 2 ? 1 : 0;
   p.win_edge = (k == 2 && s.win_edge != 0) ? 1 : 0;
   p.win_split = (k == 2 && s.win_split != 0) ? 1 : 0;
@@ -72,7 +76,7 @@ PlanSharing plan_sharing(const PlanRequest &r, const PlanSwitches &s, const Plan
   // Mirror mode of the window kernel (lrp_win_kernel.h QMode): both axes without a rotation; rows only for a pan,
   // columns only for a pitch into a rectilinear target.  Signed zeros count as zeros in the matrix tests.
   p.win_mode = p.quad == 1 ? 1 : 0;
-  const bool mirror_modes = p.window1 && !r.band && sharing && !eqs && s.mirror_modes != 0;
+  const bool mirror_modes = p.window1 && !r.band && sharing && !ext && s.mirror_modes != 0;
   // equidistant target that is not fully mirrored (a rotation, or an equirectangular source): the four mirror pixels
   // still share the ray through the output lens
   // (not for a batch: its wavefronts share ALL of the coordinate math between up to 16 frames on plain blocks at
@@ -104,7 +108,7 @@ PlanSharing plan_sharing(const PlanRequest &r, const PlanSwitches &s, const Plan
   // per 4K frame — and need no entry)
   // (... and a rectilinear source under a rectilinear / equirectangular target: four divides a pixel cost less than the 8 bytes
   // a pixel the map adds to these memory-bound kernels — rect -> equirect nearest 105 -> 117 us, bilinear 144 -> 159 with it)
-  const bool cheap_coordinates = r.in_mode == kPlanInRect && !out_eqd && r.out_type != kPlanEquisolid;
+  const bool cheap_coordinates = r.in_mode == kPlanInRect && !out_eqd && !ext_out(r.out_type);
   // Batched bilinear launches read the map too, a frame per workgroup (8 wavefronts per SIMD against the 4 of the instantiations
   // that hold coordinates across frames: equirect -> fisheye rotated 129.4 -> 107.1 us per frame, equirect -> rect 89.3 -> 84.3);
   // batched nearest keeps the frame loop (69.4 against 72.9 us).
@@ -151,7 +155,7 @@ PlanGeo plan_geo(const PlanRequest &r, const PlanSwitches &s, const PlanSharing 
   // (lrp_geo_lists.hip) says that at least kBigWidePercent % of its in-view blocks have windows the 10 KiB buffer of the
   // four-wavefront kernels cannot stage (a cubemap's pole faces: 97 -> 80 us, a rectilinear view into a fisheye frame
   // 160 -> 145; a cubemap's side faces and the ~1:1 mappings have no such block and lose 25-30 % there).
-  const bool wide = g.mode == 2 && g.lists && r.in_mode != kPlanInEquidistant && r.in_mode != kPlanInEquisolid && g.n_inview != 0 &&
+  const bool wide = g.mode == 2 && g.lists && r.in_mode != kPlanInEquidistant && !ext_in(r.in_mode) && g.n_inview != 0 &&
                     (unsigned long long)g.n_wide * 100u >= (unsigned long long)g.n_inview * kBigWidePercent;
   p.big_windows = s.geo_big == 2 ? 1 : s.geo_big != 0 ? ((p.rgbaz_runs != 0 || wide) ? 1 : 0) : 0; // (2: wherever the variant is instantiated)
   // Rendering by block class (lrp_params.h "Block lists"): once the lists of the entry are known, the corner blocks

@@ -20,10 +20,11 @@
 namespace lrp {
 
 // Numbering of lrp_params.h (static_asserts in lrp_capi.cpp keep the two in step).
-// kPlanEquisolid / kPlanInEquisolid: the opt-in lens extension (lrp_lens_extensions): plain blocks and pixels only — no
-// output-lens tables, no column-separable x, no mirror mode; the geometry cache as for the equidistant lens.
-enum PlanLens : int { kPlanRect = 0, kPlanEquidistant = 1, kPlanEquisolid = 2, kPlanEquirect = 4 };
-enum PlanInMode : int { kPlanInRect = 0, kPlanInEquidistant = 1, kPlanInEquirect = 2, kPlanInEquirectLoop = 3, kPlanInEquisolid = 4 };
+// kPlanEquisolid / kPlanInEquisolid, kPlanStereographic / kPlanInStereographic: the opt-in lens extensions
+// (lrp_lens_extensions): plain blocks and pixels only — no output-lens tables, no column-separable x, no mirror mode; the
+// geometry cache as for the equidistant lens.
+enum PlanLens : int { kPlanRect = 0, kPlanEquidistant = 1, kPlanEquisolid = 2, kPlanStereographic = 3, kPlanEquirect = 4 };
+enum PlanInMode : int { kPlanInRect = 0, kPlanInEquidistant = 1, kPlanInEquirect = 2, kPlanInEquirectLoop = 3, kPlanInEquisolid = 4, kPlanInStereographic = 5 };
 enum PlanInterp : int { kPlanNearest = 0, kPlanBilinear = 1, kPlanBicubic = 2 };
 
 // Listed launches render one block per wavefront, the enumerating launch strips of two (its wavefronts fetch the next block's

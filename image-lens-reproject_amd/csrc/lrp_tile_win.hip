@@ -33,18 +33,27 @@ hipError_t launch_win_bicubic_c5_m0_eqs(const KParams &P, int out_lens, int in_m
 hipError_t launch_win_bicubic_ss_c3_eqs(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_eqs_wins3.hip
 hipError_t launch_win_bicubic_ss_c4_eqs(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_eqs_wins4.hip
 hipError_t launch_win_bicubic_ss_c5_eqs(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_eqs_wins5.hip
+// ... and for the cells with a stereographic lens (kStgCells), the same way
+hipError_t launch_win_bicubic_c3_m0_stg(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_stg_win3.hip
+hipError_t launch_win_bicubic_c4_m0_stg(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_stg_win4.hip
+hipError_t launch_win_bicubic_c5_m0_stg(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_stg_win5.hip
+hipError_t launch_win_bicubic_ss_c3_stg(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_stg_wins3.hip
+hipError_t launch_win_bicubic_ss_c4_stg(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_stg_wins4.hip
+hipError_t launch_win_bicubic_ss_c5_stg(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_stg_wins5.hip
 // P.channels must be 3, 4 or 5, P.num_samples 1 to 4; P.win_mode = the mirror mode (lrp_kernel_v2.h QMode).
 // P.geo_mode == 2: the instantiations that load their coordinates from the geometry cache (plain blocks).
 // P.num_samples 2, 3, 4: the supersampling instantiations (plain blocks; P.geo_mode 1 / 2: they write / read an entry of sub-samples).
 hipError_t launch_win_bicubic(const KParams &P, int out_lens, int in_mode, hipStream_t stream) {
   using Fn = hipError_t (*)(const KParams &, int, int, hipStream_t);
-  const bool eqs = launch_cell_set(P, out_lens, in_mode) == kEqsCells;
+  const CellSet set = launch_cell_set(P, out_lens, in_mode);
+  const bool eqs = set == kEqsCells, stg = set == kStgCells;
   if (P.num_samples >= 2) {
     static const Fn ss_table[3] = {launch_win_bicubic_ss_c3, launch_win_bicubic_ss_c4, launch_win_bicubic_ss_c5};
     static const Fn ss_eqs_table[3] = {launch_win_bicubic_ss_c3_eqs, launch_win_bicubic_ss_c4_eqs, launch_win_bicubic_ss_c5_eqs};
+    static const Fn ss_stg_table[3] = {launch_win_bicubic_ss_c3_stg, launch_win_bicubic_ss_c4_stg, launch_win_bicubic_ss_c5_stg};
     static const Fn ssg_table[3] = {launch_win_bicubic_ssg_c3, launch_win_bicubic_ssg_c4, launch_win_bicubic_ssg_c5};
     if (P.win_mode != 0 || P.geo_mode == 3) return hipErrorInvalidValue;
-    return (P.geo_mode == 2 ? ssg_table : eqs ? ss_eqs_table : ss_table)[P.channels - 3](P, out_lens, in_mode, stream); // (2: the entry of sub-samples is read)
+    return (P.geo_mode == 2 ? ssg_table : eqs ? ss_eqs_table : stg ? ss_stg_table : ss_table)[P.channels - 3](P, out_lens, in_mode, stream); // (2: the entry of sub-samples is read)
   }
   if (P.geo_mode == 2) {
     static const Fn geo_table[3] = {launch_win_bicubic_geo_c3, launch_win_bicubic_geo_c4, launch_win_bicubic_geo_c5};
@@ -57,8 +66,10 @@ hipError_t launch_win_bicubic(const KParams &P, int out_lens, int in_mode, hipSt
        launch_win_bicubic_c4_m2, launch_win_bicubic_c4_m3, launch_win_bicubic_c4_m4},
       {launch_win_bicubic_c5_m0, launch_win_bicubic_c5_m1, launch_win_bicubic_c5_m2, launch_win_bicubic_c5_m3, launch_win_bicubic_c5_m4}};
   static const Fn eqs_table[3] = {launch_win_bicubic_c3_m0_eqs, launch_win_bicubic_c4_m0_eqs, launch_win_bicubic_c5_m0_eqs};
+  static const Fn stg_table[3] = {launch_win_bicubic_c3_m0_stg, launch_win_bicubic_c4_m0_stg, launch_win_bicubic_c5_m0_stg};
   if (P.win_mode < 0 || P.win_mode > 4) return hipErrorInvalidValue;
   if (eqs && P.win_mode == 0) return eqs_table[P.channels - 3](P, out_lens, in_mode, stream);
+  if (stg && P.win_mode == 0) return stg_table[P.channels - 3](P, out_lens, in_mode, stream);
   return table[P.channels - 3][P.win_mode](P, out_lens, in_mode, stream);
 }
 } // namespace lrp

@@ -39,7 +39,8 @@ typedef enum lrp_lens_type {
   LRP_FISHEYE_EQUIDISTANT = 1,
   LRP_FISHEYE_EQUISOLID = 2,     /* declared by the reference, rejected by reproject(); rendered here once
                                     lrp_lens_extensions(LRP_LENS_EXT_EQUISOLID) is set */
-  LRP_FISHEYE_STEREOGRAPHIC = 3, /* declared by the reference, rejected by reproject() */
+  LRP_FISHEYE_STEREOGRAPHIC = 3, /* declared by the reference, rejected by reproject(); rendered here once
+                                    lrp_lens_extensions(LRP_LENS_EXT_STEREOGRAPHIC) is set */
   LRP_EQUIRECTANGULAR = 4
 } lrp_lens_type;
 
@@ -57,6 +58,26 @@ typedef enum lrp_lens_type {
  * circle (r_mm > 2f: asinf gives NaN) have NaN rays and render what the samplers make of NaN coordinates, like the
  * centre of an equidistant output.  Rays behind the camera fold through x / -z, as for the equidistant source. */
 #define LRP_LENS_EXT_EQUISOLID 1
+/* LRP_LENS_EXT_STEREOGRAPHIC: LRP_FISHEYE_STEREOGRAPHIC, likewise declared and rejected by the reference, renders on either
+ * side.  The reference has no stereographic code; this project defines the mapping: the conformal fisheye (the "little planet"
+ * projection of a panorama), r = 2 f tan(theta / 2).  It follows the equidistant and equisolid lenses in everything but the
+ * radial law — image-circle scale by sensor_width / img_w only, target rays with z = cos(theta), source rays folded through
+ * x / -z (the front hemisphere), sensor_height not used — and needs no libm call.  Binary32, un-fused, associated left to
+ * right, F = 2.0f * focal_length (exact):
+ *   stereographic_to_vec:  r_px = sqrtf(cx*cx + cy*cy); r_mm = r_px / img_w * sensor_width;
+ *                          t = r_mm / F; t2 = t*t; d = 1.0f + t2;
+ *                          s = ((2.0f * t) / d) / r_px;               (sin(theta) / r_px)
+ *                          x = s * cx; y = s * cy; z = (1.0f - t2) / d   (cos(theta))
+ *   vec_to_stereographic:  x = x / -z; y = y / -z; r = sqrtf(x*x + y*y);
+ *                          t = r / (1.0f + sqrtf(1.0f + r*r));        (tan(atan(r) / 2))
+ *                          r_mm = F * t; r_px = r_mm / sensor_width * img_w;
+ *                          cx = x / r * r_px; cy = y / r * r_px
+ * The radius is finite for every theta < pi: there is no "beyond the image circle", every pixel has a finite ray (a full
+ * equirectangular panorama fits into one stereographic frame).  The centre pixel of an odd-sized output (r_px == 0) has a
+ * NaN ray, like the equidistant centre.  The lens has one parameter, focal_length.
+ * The value is 0x100: the low byte of the mask is spoken for (a mask of 0xFF reads back as LRP_LENS_EXT_EQUISOLID).  A
+ * reprojection between an equisolid and a stereographic lens needs both bits. */
+#define LRP_LENS_EXT_STEREOGRAPHIC 0x100
 
 /* reference src/reproject.hpp:16-20 (enum Interpolation) */
 typedef enum lrp_interpolation { LRP_NEAREST = 0, LRP_BILINEAR = 1, LRP_BICUBIC = 2 } lrp_interpolation;
@@ -88,6 +109,7 @@ typedef struct lrp_lens {
     struct { float focal_length; } rectilinear;
     struct { float fov; } fisheye_equidistant;
     struct { float focal_length; float fov; } fisheye_equisolid;
+    struct { float focal_length; } fisheye_stereographic;
     struct { float latitude_min, latitude_max, longitude_min, longitude_max; } equirectangular;
     float raw[4];
   } u;
@@ -118,7 +140,8 @@ typedef struct lrp_post {
 int lrp_abi_version(void);
 /* Process-wide mask of opt-in lens extensions (LRP_LENS_EXT_*), 0 by default: every entry point then rejects the lenses
  * the reference rejects, with its messages.  Sets the mask for subsequent calls of all threads (each call reads it once)
- * and returns the previous one; a negative value only queries.  LRP_FISHEYE_STEREOGRAPHIC stays rejected. */
+ * and returns the previous one; a negative value only queries.  The known bits (LRP_LENS_EXT_EQUISOLID,
+ * LRP_LENS_EXT_STEREOGRAPHIC) are kept, the rest dropped.  With both on, every value of lrp_lens_type renders. */
 int lrp_lens_extensions(int mask);
 /* Number of usable HIP devices (0 when there is none; never negative). */
 int lrp_device_count(void);
@@ -348,6 +371,8 @@ void lrp_lens_equirectangular_full(lrp_lens *lens);
 /* equisolid (the LRP_LENS_EXT_EQUISOLID extension): sensor_height = res_y / res_x * sensor_width, as the CLI's --equisolid
  * (src/main.cpp:45); fov is carried, not used by the mapping. */
 void lrp_lens_equisolid(lrp_lens *lens, float focal_length, float sensor_width, float fov, float res_x, float res_y);
+/* stereographic (the LRP_LENS_EXT_STEREOGRAPHIC extension): sensor_height = res_y / res_x * sensor_width, like the equisolid lens. */
+void lrp_lens_stereographic(lrp_lens *lens, float focal_length, float sensor_width, float res_x, float res_y);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@
 //   --geo 0: single launches compute their coordinates in every launch (geometry cache off); --set: lrp_debug_set
 //   --first: before the warm-up, a 256^2 twin of the workload loads its kernels, the caches are released and the workload's first
 //   launch is timed on its own (with the geometry cache on, the launch that fills the entry)
-//   eqs_* workloads: the equisolid lens extension (lrp_lens_extensions), switched on for the run
+//   eqs_* / stg_* workloads: the equisolid / stereographic lens extensions (lrp_lens_extensions), switched on for the run
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -46,7 +46,7 @@
 
 struct Workload {
   const char *name;
-  const char *in_lens, *out_lens; // "rect" | "eqd" | "eqr" | "eqrp" | "eqs"
+  const char *in_lens, *out_lens; // "rect" | "eqd" | "eqr" | "eqrp" | "eqs" | "stg"
   int interp;
   int has_rot;
   float rot_deg[3];
@@ -83,6 +83,9 @@ static const Workload kWorkloads[] = {
     // configs[2] twin (beside eqd_rect_bc / eqr_eqd_bl_rot)
     {"eqs_rect_bc", "eqs", "rect", 2, 0, {0, 0, 0}},
     {"eqr_eqs_bl_rot", "eqr", "eqs", 1, 1, {30, -15, 5}},
+    // the stereographic lens extension: the twins of the two above (same focal length and sensor)
+    {"stg_rect_bc", "stg", "rect", 2, 0, {0, 0, 0}},
+    {"eqr_stg_bl_rot", "eqr", "stg", 1, 1, {30, -15, 5}},
 };
 
 static void make_lens(lrp_lens *L, const char *kind, int w, int h) {
@@ -92,6 +95,8 @@ static void make_lens(lrp_lens *L, const char *kind, int w, int h) {
     lrp_lens_equidistant(L, 3.14159265f);
   else if (!strcmp(kind, "eqs"))
     lrp_lens_equisolid(L, 12.5f, 36.0f, 3.14159265f, (float)w, (float)h);
+  else if (!strcmp(kind, "stg"))
+    lrp_lens_stereographic(L, 12.5f, 36.0f, (float)w, (float)h);
   else if (!strcmp(kind, "eqrp")) {
     float v[4] = {-1.0f, 1.5f, -0.6f, 0.7f};
     if (const char *e = getenv("KBENCH_EQRP")) sscanf(e, "%f,%f,%f,%f", &v[0], &v[1], &v[2], &v[3]);
@@ -149,7 +154,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "no HIP device\n");
     return 1;
   }
-  lrp_lens_extensions(LRP_LENS_EXT_EQUISOLID); // (the eqs_* workloads; the others do not see the switch)
+  lrp_lens_extensions(LRP_LENS_EXT_EQUISOLID | LRP_LENS_EXT_STEREOGRAPHIC); // (the eqs_* / stg_* workloads; the others do not see the switch)
   HIP_OK(hipSetDevice(0));
   hipStream_t stream;
   HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
