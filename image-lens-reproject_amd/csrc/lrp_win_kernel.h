@@ -38,6 +38,23 @@ __device__ unsigned long long g_wave_stamps[3 * 65536];
 __device__ unsigned g_tier_stats[8]; // coefficient, raw, direct, corner, beyond a row, beyond a column, split
 #endif
 
+// Per-pass lane state of the one-block frame-loop kernels (Frames && GeoRead).  A wavefront of those renders ONE block for up
+// to 16 frames, and what a lane needs of a pass is a matter of the geometry alone: the two weights, where its taps lie in the
+// window, where its pixel goes.  How much of that an instantiation holds in registers across the frame loop instead of
+// re-deriving it in every pass of every frame — as far as its register budget goes at its occupancy (128 VGPRs at four
+// wavefronts per SIMD, RGBAZ 168 at three) without a spill:
+//   0  nothing: the coordinates are held, every pass truncates, subtracts, multiplies and clamps again
+//   1  fx, fy and ONE window byte address per pass (12 registers for the 8 of the coordinates)
+//   2  ... and the byte offset of the pass's pixel from the block's first pixel (4 more): the frame's base stays scalar
+// RGBAZ and the rectilinear source's RGB kernel stop at 1: with the offsets they spill (10 and 2 VGPRs); everything else
+// takes 2 (profiles/r08_frame_loop_pass_state.txt has the resource lines).
+constexpr int frame_loop_hoist(int in_mode, int ch) {
+  return (ch == 5 || (in_mode == kInRect && ch == 3)) ? 1 : 2;
+}
+// an LDS byte address (a multiple of the size of T) as a pointer; the reads through it are ds_read: the address space is inferred from the cast
+template <class T> __device__ __forceinline__ const T *lds_ptr(uint32_t byte_addr) {
+  return static_cast<const T *>(__builtin_assume_aligned((const T *)(__attribute__((address_space(3))) const T *)(uintptr_t)byte_addr, sizeof(T)));
+}
 
 // One wavefront walks its strip of `blocks_per_wave` blocks (plain: top to bottom; mirrored: a
 // quadrant block and its three mirror images):
@@ -166,6 +183,8 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
   // or plan of its record, no block loop.  (Carried for a second block that never came, that state cost the headline
   // instantiation 14 spilled SGPRs, 6 spilled VGPRs and two scratch reloads behind the sample of every pass.)
   constexpr bool kOneBlock = Frames && GeoRead;
+  // ... and what a lane needs of a pass is the same in every frame of that block: see PassLane below.
+  constexpr int kHoist = kOneBlock ? frame_loop_hoist(InMode, CH) : 0;
   constexpr bool Loop = (InMode == kInEquirectLoop);
   // Edge blocks (WinBlockT::edge) are compiled for the rectilinear source only: a narrow view inside a wider target is
   // where whole blocks lie beyond one side of the source; in the other instantiations the extra code costs 2-3 % (measured:
@@ -187,6 +206,9 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
   // Pass windows (below) for rectilinear targets only — perspective views and cubemap faces out of a panorama; in the
   // fisheye-target kernels the extra code cost 2.5 % (equirect -> fisheye single launches 247 -> 253 us).
   constexpr bool kPassWin = (kSplit || (GeoRead && OutLens == kEquirect)) && (OutLens == kRect || GeoRead || (InMode == kInRect && CH == 5));
+  // (the passes of a kernel that holds its lane state dispatch the tiers from that state, below: staged tiers and gathers only)
+  static_assert(kHoist == 0 || (!kSplit && !kPassWin && !kBigWin && !SS && QMode == 0),
+                "the held-state pass bodies have no split half, no pass window, no rolled loop, no mirror image");
   // (the big-window variant has no coefficient tier — its blocks are minified, the planes rarely fit: rect -> equirect RGBAZ + tonemap
   // 258 -> 252.5 us batched, RGBA 158.4 -> 156.4)
   constexpr bool kCoefHere = !kBigWin;
@@ -917,6 +939,18 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
   // may still be outstanding when the next block waits: vmcnt(1).  (Every lane stores,
   // see below, so that store is always issued.)
   WinBlock cur, nxt;
+  // Per-pass lane state (kHoist, frame_loop_hoist above), filled in front of the block's first frame and indexed by the
+  // unrolled pass number only: registers, never an indexed private array.
+  //   a, b   the weights fx, fy — of a block that gathers its taps: the coordinates themselves
+  //   addr   LDS byte address of the pixel's first read: the second tap row (coefficient tier), tap (-1, -1) (raw taps), the
+  //          plane entry of its first tap column (edge row), its first tap (edge column)
+  //   dst    byte offset of its (clamped) pixel from the block's first pixel
+  struct PassLane {
+    float a, b;
+    uint32_t addr, dst;
+  };
+  PassLane pl[4] = {};
+  size_t blk_dst_bytes = 0; // the block's first pixel in a frame (scalar)
   if constexpr (GeoRead) {
     const int cls0 = geo_class(0);
     if (cls0 == 0) geo_fetch(0, cur);
@@ -972,7 +1006,7 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
     // (the four clamped rows of a mirrored strip are loop-invariant; hoisted they occupy four VGPRs for the whole
     // strip — which spilled — so the row is re-derived from an opaque copy here: an add and a min per pass)
     int y_base = y_lane;
-    asm volatile("" : "+v"(y_base)); // (likewise not hoisted out of the frame loop)
+    if constexpr (kHoist < 2) asm volatile("" : "+v"(y_base)); // (likewise not hoisted out of the frame loop; kHoist 2: the offset is held, the row is not needed again)
     const int yk = y_base + (quad ? 0 : kBlockRows * block_row(g)) + (SS ? k : kPassRows * k);
     const int yc = yk < qh ? yk : qh - 1;
     const int gm = image_of(g);
@@ -988,6 +1022,10 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
     o.row_step = myo ? -P.out_w : P.out_w;
     return o;
   };
+  // kHoist 2: where this lane's pixel of pass k goes in the frame being rendered — the frame's base and the block's first pixel
+  // are scalar, the lane's share is a 32-bit offset (16 rows of an image: it fits), so the store takes its address as an SGPR
+  // pair + a VGPR offset and no 64-bit address is built per pass.  The same address as pass_out's, clamped lanes included.
+  auto pass_dst = [&](int k) { return reinterpret_cast<float *>(reinterpret_cast<char *>(P.dst) + blk_dst_bytes + (size_t)pl[k].dst); };
   // SS: does this lane's pixel of pass k of block g exist (its column inside the image, its row inside the band)?  Lanes beyond
   // recompute the pixel they were clamped to and store nothing.
   auto ss_inside = [&](int g, int k) { return x < qw && pixel_row(g, k) < qh; };
@@ -1018,7 +1056,13 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
       }
      }
     }
-    store_px<CH, true>(P, (uint32_t)o.yo * (uint32_t)P.out_w + (uint32_t)o.xo, a);
+    if constexpr (kHoist >= 2) {
+      float c[5];
+      finish_px<CH, true>(P, a, c);
+      store_texel_nt<CH>(pass_dst(k), c);
+    } else {
+      store_px<CH, true>(P, (uint32_t)o.yo * (uint32_t)P.out_w + (uint32_t)o.xo, a);
+    }
   };
   // A corner block: every pixel is the one value `s`.  Finished (normalize, tonemap) once, stored four times; an RGBAZ pass that
   // lies in the image whole leaves as 80 sixteen-byte chunks of the repeating five-float pattern straight from registers (no
@@ -1069,7 +1113,10 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
           continue;
         }
       }
-      store_texel_nt<CH>(P.dst + (size_t)((uint32_t)o.yo * (uint32_t)P.out_w + (uint32_t)o.xo) * CH, c);
+      if constexpr (kHoist >= 2)
+        store_texel_nt<CH>(pass_dst(k), c);
+      else
+        store_texel_nt<CH>(P.dst + (size_t)((uint32_t)o.yo * (uint32_t)P.out_w + (uint32_t)o.xo) * CH, c);
     }
   };
   // Pass windows (kernels with split blocks): a block whose two half windows do not fit either (a pole face of a
@@ -1231,6 +1278,40 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
     request_taps(psx, psy);
     return 2;
   };
+  // The one-block frame-loop kernels: the lane state of the four passes, once per block (behind the request of the first
+  // frame's window: its round trip covers this).  The tier is wave-uniform, so what `a`, `b` and `addr` mean is too.
+  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)win0;
+  if constexpr (kHoist >= 1) {
+    const int tier = cur.tier; // (scalar: made uniform above)
+    const int edge = kEdge ? ((tier >> 6) & 7) : 0;
+    const int x_blk = tx * (kBlkW * kWinWaves) + wave * kBlkW, y_blk = P.y_offset + ty * kBlockRows; // the block's first pixel (scalar)
+    if constexpr (kHoist >= 2) blk_dst_bytes = (size_t)((uint32_t)y_blk * (uint32_t)P.out_w + (uint32_t)x_blk) * (4u * CH);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float psx = cur.sx[k], psy = cur.sy[k];
+      const float tx_ = __builtin_truncf(psx), ty_ = __builtin_truncf(psy);
+      int slot = 0;
+      pl[k].a = psx - tx_;
+      pl[k].b = psy - ty_;
+      if (edge != 0) {
+        slot = edge < 3 ? cur.c_base + ((int)tx_ - 1 - cur.x_lo) : (int)ty_ - 1 - cur.y_lo;
+      } else if (kCoefHere && (tier & 2) != 0) {
+        // one 24-bit multiply per pixel (a 32-bit v_mul_lo_u32 issues at quarter rate); every other term
+        // of the address is wave-uniform and folded into tap_base when the block is planned
+        slot = __mul24((int)ty_, cur.spitch()) + (int)tx_ + cur.tap_base; // window slot of (int(sx) - 1, int(sy)): the second tap row
+      } else if ((tier & 1) != 0) {
+        slot = cur.org() + __mul24((int)ty_ - 1 - cur.y_lo, cur.spitch()) + ((int)tx_ - 1 - cur.x_lo);
+      } else { // nothing staged (or a corner block, which reads neither): the gathers take the coordinates
+        pl[k].a = psx;
+        pl[k].b = psy;
+      }
+      pl[k].addr = lds0 + (uint32_t)slot * 16u;
+      if constexpr (kHoist >= 2) {
+        const PassOut o = pass_out(0, k);
+        pl[k].dst = (uint32_t)((o.yo - y_blk) * P.out_w + (o.xo - x_blk)) * (4u * CH);
+      }
+    }
+  }
 #pragma unroll 1
   for (int g = 0; g < G; ++g) {
    g_loop = g;
@@ -1244,8 +1325,9 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
    for (int f = 0; f < n_frames; ++f) {
     f_loop = f;
     // (one block: everything derived from the block record is the same in every frame, and what is per lane of it — LDS
-    // addresses of the planes, DMA offsets, masks — gets hoisted out of the frame loop into registers the passes need: opaque,
-    // those few adds and shifts run per frame)
+    // addresses of precompute()'s reads and writes, DMA offsets, masks — gets hoisted out of the frame loop into registers
+    // the passes need: opaque, those few adds and shifts run per frame.  What the PASSES need per lane is held on purpose,
+    // as much of it as fits: pl[], kHoist.)
     if constexpr (kOneBlock) asm volatile("" : "+v"(lane));
     if (n_frames > 1 || g == 0) set_frame(f);
     const bool last_frame = f + 1 == n_frames; // the next step is the next block
@@ -1262,7 +1344,10 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
     // The tier of this block in a scalar register for the branches below: carried through the block loop inside `cur` it
     // ends up in a VGPR (the kernel is at the SGPR limit), and every test of it then costs a v_and + v_cmp and the
     // branch condition is re-materialised through v_cndmask / v_cmp at each use — seven VALU instructions per pass.
-    const int tier = __builtin_amdgcn_readfirstlane(cur.tier);
+    int tier = __builtin_amdgcn_readfirstlane(cur.tier);
+    // (kHoist: the block record is scalar and the same in every frame — the flags below from an opaque copy made per frame
+    // are scalar compares; hoisted out of the frame loop as lane masks they come back through v_cndmask / v_cmp)
+    if constexpr (kHoist >= 1) asm volatile("" : "+s"(tier));
     const bool t_coef = kCoefHere && (tier & 2) != 0, t_staged = (tier & 1) != 0, t_whole = (tier & 4) != 0;
     const int t_edge = kEdge ? ((tier >> 6) & 7) : 0;
     const bool t_split = kSplit && (tier & 512) != 0; // the window holds passes 0-1; that of passes 2-3 is fetched behind pass 1's taps // 1, 2: beyond the first / last source row; 3, 4: column
@@ -1386,7 +1471,8 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
       if (t_coef && (h == 0 || !t_whole)) precompute(cur, h);
       // (the RGBAZ big-window variant keeps the two passes of a half rolled — its code shrinks 82 -> 77 KB: rect -> equirect RGBAZ +
       // tonemap 262 -> 255 us batched; RGB / RGBA lose 0.5-1.5 % that way and stay unrolled)
-      float hx0 = cur.sx[2 * h], hx1 = cur.sx[2 * h + 1], hy0 = cur.sy[2 * h], hy1 = cur.sy[2 * h + 1];
+      float hx0 = 0.0f, hx1 = 0.0f, hy0 = 0.0f, hy1 = 0.0f;
+      if constexpr (kHoist == 0) hx0 = cur.sx[2 * h], hx1 = cur.sx[2 * h + 1], hy0 = cur.sy[2 * h], hy1 = cur.sy[2 * h + 1];
       if constexpr (kBigWin && CH == 5) asm volatile("" : "+v"(hx0), "+v"(hx1), "+v"(hy0), "+v"(hy1)); // (selected, not indexed: no scratch)
 #pragma unroll(kBigWin && CH == 5 ? 1 : 2)
       for (int kk = 0; kk < 2; ++kk) {
@@ -1400,17 +1486,49 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
         // (where the coordinates of a mirror image are a plain selection of stored values the compiler would otherwise
         // hoist everything derived from them — truncations, weights, window addresses of all four passes and both
         // images — out of the block loop and spill it: the selected values are opaque here)
-        // (the same goes for the frame loop: everything derived from the coordinates of a pass is the same in every frame,
-        // and kept for all four passes it does not fit the registers — what IS shared between frames is stage 1 and the
-        // window plan, by construction)
-        asm volatile("" : "+v"(psx), "+v"(psy));
+        // (the frame loop of a strip of blocks: everything derived from the coordinates of a pass is the same in every frame,
+        // and kept for all four passes of two blocks it does not fit the registers.  The one-block kernels hold the part of
+        // it that the passes need — pl[k] — and these coordinates are not read: nothing to hide.)
+        if constexpr (kHoist == 0) asm volatile("" : "+v"(psx), "+v"(psy));
         Rgba s;
         // behind the pixel's last read of the window: the next window's DMA (last pass), the second half of a split block (pass 1)
         auto after_reads = [&]() {
           if (last_pass) next_window();
           if (t_split && k == 1) issue(P.src, cur, 1);
         };
-        if (t_edge != 0) {
+        if constexpr (kHoist >= 1) {
+          // The tiers from the held lane state: the same reads, the same operations on the same operands as below.  Per pass
+          // and frame: the plane addresses (one wave-uniform add each) and hfx, hfy.
+          // (The state is held, what derives from it is not: three plane addresses and two products per pass — or the sixteen
+          // tap addresses of a pass that gathers — kept for all four passes do not fit the registers.  So the compiler is
+          // told that the state changes from frame to frame, in place: no instruction, no copy, nothing to hoist.)
+          asm volatile("" : "+v"(pl[k].a), "+v"(pl[k].b), "+v"(pl[k].addr));
+          if constexpr (kHoist >= 2) asm volatile("" : "+v"(pl[k].dst));
+          const PassLane q = pl[k];
+          // RGBAZ: the pixel's first depth tap, `plane_bytes` = LDS offset of the float plane (+ what the tier's depth slot
+          // differs from its colour slot by); a depth slot is a quarter of a colour slot
+          auto depth_at = [&](int plane_bytes) { return lds_ptr<float>((q.addr >> 2) + (lds0 - (lds0 >> 2)) + (uint32_t)plane_bytes); };
+          if (t_edge != 0) {
+            if (t_edge < 3) // beyond the first / last source row
+              s = win_tier_edge_row<CH>(lds_ptr<float4>(q.addr), depth_at((cur.c_base + cur.bw) * 16 - cur.c_base * 4), q.a, after_reads);
+            else // beyond the first / last source column
+              s = win_tier_edge_col<CH>(lds_ptr<float4>(q.addr), depth_at(cur.bh * 16), q.b, t_edge == 4 ? 1.0f : 0.0f, after_reads);
+          } else if (t_coef) {
+            s = win_tier_coef<CH>(lds_ptr<float4>(q.addr), lds_ptr<float4>(q.addr + (uint32_t)(cur.c_delta(h) * 16)), cur.c_plane, cur.pitch,
+                                  depth_at(cur.pitch * cur.bh * 16 - cur.spitch() * 4), q.a, q.b, after_reads);
+          } else if (t_staged) {
+            s = win_tier_raw<CH>(lds_ptr<float4>(q.addr), cur.spitch(), depth_at(cur.pitch * cur.bh * 16), q.a, q.b, after_reads);
+          } else {
+            if (last_pass) next_window(); // nothing staged: no tap of this block reads the window
+            const float gx = q.a, gy = q.b;
+            if constexpr (CH == 5) {
+              const Px<5> s5 = sample_direct<2, Loop, 5, LRP_WIN_MINWAVES5 >= 4>(P, src, gx, gy);
+              s = Rgba{s5.lo, s5.hi, s5.e};
+            } else {
+              s = sample_direct<2, Loop, 4, (LRP_WIN_MINWAVES >= 5), 4 * CH>(P, src, gx, gy);
+            }
+          }
+        } else if (t_edge != 0) {
           if (t_edge < 3) { // beyond the first / last source row
             const float tx_ = __builtin_truncf(psx);
             const int slot = (int)tx_ - 1 - cur.x_lo;
