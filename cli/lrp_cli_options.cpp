@@ -47,6 +47,7 @@ const Option kOptions[] = {
     {"allow-equisolid", 0, false, nullptr, "", "Render equisolid fisheye lenses (--equisolid, --i-equisolid, FISHEYE_EQUISOLID configs; r = 2 f sin(theta / 2)): an extension, the reference rejects them.", "Output optics"},
     {"allow-stereographic", 0, false, nullptr, "", "Render stereographic fisheye lenses (--stereographic, --i-stereographic, FISHEYE_STEREOGRAPHIC configs; r = 2 f tan(theta / 2), the little-planet projection): an extension, the reference rejects them.", "Output optics"},
     {"rotation", 0, true, "0.0", "pan,pitch,roll (degrees)", "Rotate the view.", "Output optics"},
+    {"mask-outside", 0, false, nullptr, "", "Write zeros to the output pixels the input image cannot see (outside its frame, or behind the camera) instead of the reference's smeared border and mirrored ghost (MI355X addition).", "Output optics"},
     {"exposure", 0, true, "0.0", "EV", "Exposure compensation in stops.", "Color processing"},
     {"reinhard", 0, true, "1.0", "max", "Reinhard tone mapping with this maximum (after exposure).", "Color processing"},
     {"skip-if-exists", 0, false, nullptr, "", "Skip files whose outputs already exist.", "Runtime"},

@@ -122,6 +122,11 @@ void process_on_host_floats(Shared &sh, Device &dev, const lrp_io::Packed &input
     if (in.data.size() < out.data.size()) throw std::runtime_error("input smaller than the configured resolution");
     std::memcpy(out.data.data(), in.data.data(), out.data.size() * sizeof(float));
     if (plan.post_process()) check_status(sh, lrp_post_process(&cout, pp.exposure, pp.reinhard, dev.index));
+  } else if (plan.mask_outside) { // through the device's pipeline, whose contexts mask (run_files): float frames up and down
+    int ticket = -1;
+    check_status(sh, lrp_context_submit_packed(dev.pipeline, &cin, LRP_PIXEL_F32, in.channels, &cout, LRP_PIXEL_F32, out.channels, 0u,
+                                               plan.num_samples, plan.interpolation, plan.rotation, plan.post_process() ? &pp : nullptr, &ticket));
+    check_status(sh, lrp_context_wait_ticket(dev.pipeline, ticket));
   } else {
     check_status(sh, lrp_reproject(&cin, &cout, plan.num_samples, plan.interpolation, plan.rotation,
                                    plan.post_process() ? &pp : nullptr, dev.index));
@@ -213,6 +218,7 @@ RunResult run_files(const RunPlan &plan, const std::vector<fs::path> &files) {
         result.aborted = true;
         return result;
       }
+      if (plan.mask_outside) lrp_context_set_outside(devices[(size_t)g].pipeline, 1, -1); // --mask-outside
     }
   }
   Shared shared{plan, (int)files.size(), needs_gpu ? kPinned : lrp_io::heap_allocator()};

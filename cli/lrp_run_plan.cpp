@@ -149,6 +149,7 @@ int resolve_io(const CommandLine &cl, const char *argv0, RunPlan &p) {
 
 int resolve_rendering(const CommandLine &cl, const char *, RunPlan &p) {
   p.num_samples = std::atoi(cl["samples"].c_str());
+  p.mask_outside = cl.has("mask-outside");
   if (cl.has("output-resolution")) {
     const std::string arg = cl["output-resolution"];
     const size_t comma = arg.find(',');

@@ -29,6 +29,7 @@ struct RunPlan {
   int num_samples = 1, interpolation = LRP_BICUBIC;
   float rotation[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   double exposure = 1.0, reinhard = 1.0;
+  bool mask_outside = false; // --mask-outside: the output pixels the source cannot see are written as zeros (include/lrp.h "coverage")
   // outputs
   std::filesystem::path output_dir;
   bool write_exr = false, write_png = false, skip_if_exists = false, dry_run = false;

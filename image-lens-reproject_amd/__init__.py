@@ -11,7 +11,9 @@ over the C ABI of include/lrp.h (liblrp_hip.so, hand-written HIP for gfx950).
 Image data may be a C-contiguous float32 numpy array (host path: upload, kernel,
 download) or a float32 torch CUDA tensor (device-resident path, asynchronous on
 the given / current torch stream).  There is no CPU implementation here: without
-the HIP library and a GPU every compute call raises.
+the HIP library and a GPU every compute call raises.  Beyond the reference:
+coverage(in_image, out_image, num_samples, rotation_matrix) tells which output
+pixels the source image can see (device tensors).
 
 The directory name contains a hyphen (it is the name the build contract fixes);
 import it with importlib.import_module("image-lens-reproject_amd").
@@ -283,6 +285,31 @@ def reproject(in_image, out_image, num_samples, interpolation, rotation_matrix=N
     _check(st)
 
 
+def coverage(in_image, out_image, num_samples, rotation_matrix=None, out=None, mask_image=False, alpha_channel=-1, device=None,
+             stream=None):
+    """lrp_coverage_device (include/lrp.h "coverage"): how many of the num_samples^2 sub-samples of every output pixel the source
+    image recorded — inside the source rectangle and, for a source that folds rays through x / -z, in front of the camera.
+    Returns the (height, width) uint8 CUDA tensor of counts (`out` if given, else allocated).  mask_image: every channel of the
+    count-0 pixels of out_image.data (a CUDA tensor) becomes +0.0; alpha_channel >= 0: that channel of every pixel becomes
+    count / num_samples^2.  in_image.data is not read and may be None.  Asynchronous on `stream`."""
+    import torch
+
+    lib = _native.load()
+    cin, cout = in_image.to_c(), out_image.to_c()
+    keep, rot = _rotation_arg(rotation_matrix)
+    if device is None:
+        device = next((t.device.index for t in (out, out_image.data, in_image.data) if _is_torch(t) and t.is_cuda), 0)
+    if out is None:
+        out = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}")
+    elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() != out_image.height * out_image.width:
+        raise ValueError("out must be a contiguous uint8 CUDA tensor with height*width elements")
+    st = lib.lrp_coverage_device(ctypes.byref(cin), ctypes.byref(cout), int(num_samples), rot, out.data_ptr(), int(bool(mask_image)),
+                                 int(alpha_channel), device, _stream_handle(stream))
+    del keep
+    _check(st)
+    return out
+
+
 def reproject_multi(in_image, out_images, num_samples, interpolation, rotation_matrices=None, post=None, device=None,
                     stream=None):
     """One resident source, several target lenses / rotations (device tensors only)."""
@@ -434,6 +461,12 @@ class BatchContext:
                                                    int(out_fill), int(num_samples), int(interpolation), rot,
                                                    ctypes.byref(cpost) if cpost else None, ctypes.byref(ticket)))
         return ticket.value
+
+    def set_outside(self, mask_image=False, alpha_channel=-1):
+        """lrp_context_set_outside: for the images submitted from now on, the coverage kernel follows the reprojection — the
+        pixels the source cannot see become +0.0 (mask_image) and / or a channel receives the coverage fraction (alpha_channel).
+        (False, -1) switches it off."""
+        _check(self._lib.lrp_context_set_outside(self._h, int(bool(mask_image)), int(alpha_channel)))
 
     def wait_ticket(self, ticket):
         _check(self._lib.lrp_context_wait_ticket(self._h, int(ticket)))

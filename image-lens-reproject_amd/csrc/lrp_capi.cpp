@@ -2,7 +2,7 @@
 // reference's dispatch order, kernel-argument construction, device buffers,
 // streams and the batch context.  Host code only; the kernels live in the
 // lrp_kernels_*.hip / lrp_tile_*.hip / lrp_eqs_*.hip / lrp_stg_*.hip (reprojection), lrp_tables.hip, lrp_geo_lists.hip,
-// lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
+// lrp_coverage.hip (coverage planes), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +39,9 @@ hipError_t launch_ss_gather(const KParams &P, int interpolation, int in_mode, hi
 hipError_t launch_geo_build_lists(int32_t *box, int out_w, int out_h, int alias_pairs, hipStream_t stream); // lrp_geo_lists.hip
 hipError_t launch_geo_census(int32_t *box, int out_w, int out_h, int in_w, int in_h, bool clear_header, hipStream_t stream); // lrp_geo_lists.hip
 hipError_t launch_corner_fill(const KParams &P, hipStream_t stream);
+// lrp_coverage.hip.  A weak reference: the host-code test drivers (tests/native/multi_driver.cpp) link this file against stand-ins
+// of the launchers they exercise; where the unit is not linked in, a coverage request fails (enqueue_coverage).
+__attribute__((weak)) hipError_t launch_coverage(KParams P, int out_lens, int in_mode, uint8_t *plane, int mask_image, int alpha_channel, hipStream_t stream);
 hipError_t launch_post_process(float *data, uint32_t n_pixels, int channels, float exposure, float reinhard,
                                hipStream_t stream);
 hipError_t launch_synth_fill(float *data, uint32_t n_elems, int channels, uint32_t seed, int depth_channel,
@@ -503,6 +506,35 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
   return LRP_OK;
 }
 
+// lrp_coverage_device's checks: the lens, extension and size checks of validate() in its order, then the request itself.
+int validate_coverage(const lrp_image *in, const lrp_image *out, int num_samples, bool want_plane, int mask_image, int alpha_channel) {
+  if (!in || !out) return fail(LRP_ERR_NULL, "null image");
+  const int ext = g_lens_ext.load(std::memory_order_relaxed);
+  if (!lens_in_hot_path(out->lens.type, ext)) return fail(LRP_ERR_OUTPUT_LENS, "Output lens type not supported.");
+  if (!lens_in_hot_path(in->lens.type, ext)) return fail(LRP_ERR_INPUT_LENS, "Input lens type not supported.");
+  if (in->width < 1 || in->height < 1 || out->width < 1 || out->height < 1)
+    return fail(LRP_ERR_BAD_DIMS, "image dimensions must be positive");
+  const bool touches_image = mask_image != 0 || alpha_channel != -1;
+  if ((unsigned long long)out->width * (unsigned long long)out->height > kMaxImageFloats || (touches_image && out->channels >= 1 && !image_addressable(*out)))
+    return fail(LRP_ERR_BAD_DIMS, "an image of more than 2^31 floats (8 GiB) cannot be addressed (the reference indexes texels with int, src/reproject.cpp:49-51)");
+  if (!want_plane && !touches_image) return fail(LRP_ERR_BAD_ARG, "nothing requested: no coverage plane, no mask, no alpha channel");
+  if (num_samples < 1 || num_samples > 15) return fail(LRP_ERR_BAD_ARG, "num_samples of a coverage call must be 1 .. 15 (the count is one byte)");
+  if (touches_image && out->channels < 1) return fail(LRP_ERR_CHANNELS, "out->channels must be >= 1");
+  if (alpha_channel < -1 || (alpha_channel >= 0 && alpha_channel >= out->channels)) return fail(LRP_ERR_BAD_ARG, "alpha_channel outside [-1, out->channels)");
+  if (touches_image && !out->data) return fail(LRP_ERR_NULL, "null image data");
+  return LRP_OK;
+}
+
+// One launch of the coverage kernel (lrp_coverage.hip); no table, no geometry-cache entry, no allocation.
+int enqueue_coverage(const lrp_image *in, const lrp_image *out, int num_samples, const float *rotation, uint8_t *plane, int mask_image,
+                     int alpha_channel, hipStream_t stream) {
+  if (!lrp::launch_coverage) return fail(LRP_ERR_HIP, "the coverage kernels (lrp_coverage.hip) are not part of this build");
+  const lrp::KParams P = make_params(in, out, num_samples, rotation, nullptr);
+  const hipError_t e = lrp::launch_coverage(P, out->lens.type, in_lens_mode(in->lens), plane, mask_image, alpha_channel, stream);
+  if (e != hipSuccess) return hip_fail(e, "coverage kernel launch");
+  return LRP_OK;
+}
+
 // Grow-only device / pinned buffer.
 struct Buffer {
   void *ptr = nullptr;
@@ -565,6 +597,7 @@ struct lrp_context {
   unsigned run_next = 0;
   std::vector<Slot> slots;
   size_t next = 0;
+  int outside_mask = 0, outside_alpha = -1; // lrp_context_set_outside: the coverage kernel behind every reprojection (off)
 };
 
 extern "C" {
@@ -654,6 +687,15 @@ int lrp_reproject_rows_device(const lrp_image *in, lrp_image *out, int num_sampl
   if (st != LRP_OK) return st;
   if (row_count == 0) return LRP_OK;
   return enqueue_reproject(in, out, num_samples, interpolation, rotation, post, device, (hipStream_t)stream, 0, row_first, row_count);
+}
+
+int lrp_coverage_device(const lrp_image *in, const lrp_image *out, int num_samples, const float *rotation, uint8_t *coverage,
+                        int mask_image, int alpha_channel, int device, void *stream) {
+  int st = validate_coverage(in, out, num_samples, coverage != nullptr, mask_image, alpha_channel);
+  if (st != LRP_OK) return st;
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_coverage(in, out, num_samples, rotation, coverage, mask_image, alpha_channel, (hipStream_t)stream);
 }
 
 namespace {
@@ -1026,6 +1068,10 @@ int submit_locked(lrp_context *ctx, const lrp_image *in, int in_format, int in_p
   dout.data = (float *)s.d_out.ptr;
   int st = enqueue_reproject(&din, &dout, num_samples, interpolation, rotation, post, ctx->device, run);
   if (st != LRP_OK) return st;
+  if (ctx->outside_mask != 0 || ctx->outside_alpha != -1) { // lrp_context_set_outside
+    st = enqueue_coverage(&din, &dout, num_samples, rotation, nullptr, ctx->outside_mask, ctx->outside_alpha, run);
+    if (st != LRP_OK) return st;
+  }
   if (!out_plain) {
     hipError_t e = lrp::launch_encode_pixels((const float *)s.d_out.ptr, out->channels, s.d_out_packed.ptr, out_format, out_pch,
                                              out_fill, out_px, ctx->device, run);
@@ -1056,6 +1102,10 @@ int lrp_context_submit_packed(lrp_context *ctx, const lrp_image *in, int in_form
   if (st != LRP_OK) return st;
   if (num_samples <= 0) return LRP_OK; // reference loop body never runs: output untouched
   std::lock_guard<std::mutex> lock(ctx->mutex);
+  if (ctx->outside_mask != 0 || ctx->outside_alpha != -1) { // (before anything is enqueued)
+    st = validate_coverage(in, out, num_samples, false, ctx->outside_mask, ctx->outside_alpha);
+    if (st != LRP_OK) return st;
+  }
   return submit_locked(ctx, in, in_format, in_packed_channels, out, out_format, out_packed_channels, out_fill, num_samples,
                        interpolation, rotation, post, ticket);
 }
@@ -1065,6 +1115,15 @@ int lrp_context_submit(lrp_context *ctx, const lrp_image *in, lrp_image *out, in
   if (!in || !out) return fail(LRP_ERR_NULL, "null image");
   return lrp_context_submit_packed(ctx, in, LRP_PIXEL_F32, in->channels, out, LRP_PIXEL_F32, out->channels, 0u, num_samples,
                                    interpolation, rotation, post, nullptr);
+}
+
+int lrp_context_set_outside(lrp_context *ctx, int mask_image, int alpha_channel) {
+  if (!ctx) return fail(LRP_ERR_NULL, "null context");
+  if (alpha_channel < -1) return fail(LRP_ERR_BAD_ARG, "alpha_channel must be -1 or a channel index");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  ctx->outside_mask = mask_image != 0;
+  ctx->outside_alpha = alpha_channel;
+  return LRP_OK;
 }
 
 int lrp_context_wait_ticket(lrp_context *ctx, int ticket) {

@@ -251,6 +251,39 @@ int lrp_reproject_batch_device(const lrp_image *ins, lrp_image *outs, int n, int
                                int interpolation, const float *rotation, const lrp_post *post,
                                int device, void *stream);
 
+/* ---- coverage planes: which output pixels the source can see ------------------------ */
+
+/* The render entry points reproduce what the reference does with a ray the source image never recorded: its samplers clamp,
+ * so a coordinate outside the source smears the border texel (src/reproject.cpp:45-47,63-67,119-127), and the sources that
+ * fold a ray through x / -z (rectilinear :163-164, equidistant :191-192, and the two extension lenses above) render a
+ * mirrored ghost of the picture for a ray behind the camera.  The coverage of a call says which output pixels are real.
+ *
+ * Definition, for output pixel (x, y) and sub-sample (ssx, ssy) of a num_samples = n call: vx, vy, vz is the ray after the
+ * optional rotation (src/reproject.cpp:301-311), sx, sy the top-left-origin coordinates the sampler receives (:323-324) —
+ * binary32, un-fused, exactly the values the render kernels compute.  The sub-sample is COVERED iff
+ *   front:  vz < 0.0f for a source that folds through x / -z (rectilinear, equidistant, equisolid, stereographic); always
+ *           true for an equirectangular source;
+ *   in_x:   sx == sx for a wrapping source (LoopHorizontally, :386-390); sx >= -0.5f && sx <= (float)in_w - 0.5f otherwise;
+ *   in_y:   sy >= -0.5f && sy <= (float)in_h - 0.5f
+ * all hold.  Comparisons with NaN are false: a NaN ray (the centre of an odd-sized fisheye output, the area beyond the
+ * equisolid image circle) is uncovered.  The COVERAGE COUNT of a pixel is the number of its covered sub-samples, 0 .. n * n,
+ * one uint8_t per output pixel; the plane is row-major without padding.
+ *
+ * lrp_coverage_device: asynchronous on `stream`; neither allocates nor synchronises.  in->data is never read and may be NULL
+ * (in->channels is not looked at).  Whatever is requested is done by one kernel launch:
+ *   coverage        device pointer of any alignment, or NULL: receives the count plane (out->width * out->height bytes);
+ *   mask_image != 0 every channel of every pixel of out->data (a device pointer) whose count is 0 becomes +0.0f; every other
+ *                   pixel keeps its bytes;
+ *   alpha_channel   in [0, out->channels): that channel of EVERY pixel of out->data becomes (float)count * (1.0f / (float)(n * n))
+ *                   (the reference's normalize, :280), applied after the mask; -1: off.
+ * Errors: the lens, extension-mask and size errors of lrp_reproject_device, in its order and with its statuses (an equisolid
+ * or stereographic lens needs its extension bit; the interpolation check has no counterpart); then LRP_ERR_BAD_ARG for nothing
+ * requested (coverage == NULL, no mask, no alpha), num_samples < 1 or > 15, or an alpha_channel outside [-1, out->channels);
+ * LRP_ERR_CHANNELS / LRP_ERR_NULL for a mask or alpha request with out->channels < 1 / out->data == NULL.  The geometry cache
+ * is neither read nor written: the lrp_geometry_cache_stats counters do not move. */
+int lrp_coverage_device(const lrp_image *in, const lrp_image *out, int num_samples, const float *rotation,
+                        uint8_t *coverage, int mask_image, int alpha_channel, int device, void *stream);
+
 /* ---- one source, several outputs, several GPUs (BASELINE configs[4]) ---------- */
 
 /* One host source, n_out host outputs (lenses in outs[i].lens, rotations + 9 * i or none): the
@@ -283,6 +316,13 @@ int lrp_context_submit(lrp_context *ctx, const lrp_image *in, lrp_image *out, in
                        int interpolation, const float *rotation, const lrp_post *post);
 /* Wait for everything submitted so far; returns the first error seen. */
 int lrp_context_wait(lrp_context *ctx);
+
+/* What a context does with the output pixels the source cannot see (lrp_coverage_device's mask_image / alpha_channel): applies
+ * to the images submitted afterwards with lrp_context_submit and lrp_context_submit_packed.  On the image's compute stream the
+ * coverage kernel follows the reprojection and its fused post_process and runs in front of the encode kernel and the download.
+ * (0, -1) switches it off: the default, which leaves the pipeline as it is without this call.  An alpha_channel the image does
+ * not have fails that submission with LRP_ERR_BAD_ARG. */
+int lrp_context_set_outside(lrp_context *ctx, int mask_image, int alpha_channel);
 
 /* ---- pixel formats of the file path -------------- */
 

@@ -7,13 +7,15 @@
 //
 // Build (tools/build_kbench.sh):
 //   hipcc -O2 -std=c++17 tools/kbench.cpp -Iinclude -L<pkg>/lib -llrp_hip -Wl,-rpath,<pkg>/lib -o tools/kbench
-// Usage: kbench [--size N] [--reps R] [--warmup W] [--distinct D] [--channels C] [--ns S] [--batch B] [--geo 0|1] [--set name=value] [--sum] [--streams S] [workload ...]
+// Usage: kbench [--size N] [--reps R] [--warmup W] [--distinct D] [--channels C] [--ns S] [--batch B] [--geo 0|1] [--set name=value] [--sum] [--streams S] [--coverage 1|2] [workload ...]
 //   --streams S: launch i goes to stream i % S (no events in between); the figure is wall time per launch between the first launch and the
 //   last stream's completion — S = 1 and S = 2 compare back-to-back launches on one stream with launches whose tails and heads may overlap
 //   --batch B: every launch renders B frames (lrp_reproject_batch_device, B <= distinct); times are per launch / B
 //   --geo 0: single launches compute their coordinates in every launch (geometry cache off); --set: lrp_debug_set
 //   --first: before the warm-up, a 256^2 twin of the workload loads its kernels, the caches are released and the workload's first
 //   launch is timed on its own (with the geometry cache on, the launch that fills the entry)
+//   --coverage 1|2: times lrp_coverage_device of the workload's geometry instead of the reprojection — 1: the count plane alone, 2: the plane
+//   and the zero mask on the workload's output image (the sampler of the workload plays no part); --sum then hashes the plane
 //   eqs_* / stg_* workloads: the equisolid / stereographic lens extensions (lrp_lens_extensions), switched on for the run
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -117,7 +119,7 @@ static uint64_t fnv1a(const void *p, size_t n) {
 }
 
 int main(int argc, char **argv) {
-  int size = 4096, reps = 20, distinct = 4, channels = 4, ns = 1, out_size = 0, warmup = 100, batch = 0, n_streams = 0;
+  int size = 4096, reps = 20, distinct = 4, channels = 4, ns = 1, out_size = 0, warmup = 100, batch = 0, n_streams = 0, coverage = 0;
   bool sum = false, post = false, first = false;
   std::vector<std::string> names;
   for (int i = 1; i < argc; ++i) {
@@ -132,6 +134,7 @@ int main(int argc, char **argv) {
     else if (a == "--ns") ns = next();
     else if (a == "--batch") batch = next();
     else if (a == "--streams") n_streams = next();
+    else if (a == "--coverage") coverage = next();
     else if (a == "--geo") lrp_debug_set("geo_cache", next());
     else if (a == "--set" && i + 1 < argc) {
       std::string kv = argv[++i];
@@ -179,6 +182,14 @@ int main(int argc, char **argv) {
     LRP_OKAY(lrp_synth_fill_device(src[i], size, size, channels, 0x5EED0000u + i, channels == 5 ? 4 : -1, 0, stream));
   }
   HIP_OK(hipStreamSynchronize(stream));
+  uint8_t *plane = nullptr; // --coverage: the count plane
+  if (coverage) {
+    if (batch > 0 || n_streams > 0 || first) {
+      fprintf(stderr, "--coverage times single launches on one stream\n");
+      return 1;
+    }
+    HIP_OK(hipMalloc(&plane, (size_t)out_size * out_size));
+  }
   std::vector<float> host;
   if (sum) host.resize(out_elems);
   hipEvent_t e0, e1;
@@ -217,6 +228,11 @@ int main(int argc, char **argv) {
       outs[(size_t)b].data = dst[(size_t)(b % cycle("KBENCH_BATCH_DISTINCT_DST"))];
     }
     auto launch = [&](int i) {
+      if (coverage) {
+        out.data = dst[i % distinct];
+        LRP_OKAY(lrp_coverage_device(&in, &out, ns, W->has_rot ? rot : nullptr, plane, coverage == 2, -1, 0, stream));
+        return;
+      }
       if (batch > 0) {
         LRP_OKAY(lrp_reproject_batch_device(ins.data(), outs.data(), batch, ns, W->interp, W->has_rot ? rot : nullptr,
                                             post ? &pp : nullptr, 0, stream));
@@ -315,14 +331,18 @@ int main(int argc, char **argv) {
     if (sum) {
       launch(0);
       HIP_OK(hipStreamSynchronize(stream));
-      HIP_OK(hipMemcpy(host.data(), dst[0], out_elems * 4, hipMemcpyDeviceToHost));
-      h = fnv1a(host.data(), out_elems * 4);
+      HIP_OK(hipMemcpy(host.data(), coverage ? (const void *)plane : (const void *)dst[0], coverage ? (size_t)out_size * out_size : out_elems * 4, hipMemcpyDeviceToHost));
+      h = fnv1a(host.data(), coverage ? (size_t)out_size * out_size : out_elems * 4);
     }
     if (auto rd = (void (*)(unsigned *))dlsym(RTLD_DEFAULT, "lrp_debug_read_tiers")) { // diagnostic builds only
       unsigned t[4] = {0, 0, 0, 0};
       rd(t);
       printf("    window-kernel blocks per tier (all launches so far): coefficients %u, raw taps %u, direct %u\n", t[0], t[1], t[2]);
     }
+    if (coverage) // (no algorithmic-bytes figure: the kernel reads nothing and writes a byte per pixel, plus the zeros of the mask)
+      printf("%-18s coverage %s avg %8.1f us  min %8.1f us  %8.2f Gpix/s", W->name, coverage == 2 ? "plane+mask" : "plane     ", avg_s * 1e6, best * 1e3,
+             (double)out_size * out_size / avg_s / 1e9);
+    else
     printf("%-18s avg %8.1f us  min %8.1f us  %8.2f Gpix/s  %7.1f GB/s algorithmic  frac %.3f", W->name, avg_s * 1e6,
            best * 1e3, (double)out_size * out_size / avg_s / 1e9, bytes / avg_s / 1e9, bytes / avg_s / 8e12);
     if (sum) printf("  fnv %016llx", (unsigned long long)h);
