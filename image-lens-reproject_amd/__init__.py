@@ -13,7 +13,9 @@ download) or a float32 torch CUDA tensor (device-resident path, asynchronous on
 the given / current torch stream).  There is no CPU implementation here: without
 the HIP library and a GPU every compute call raises.  Beyond the reference:
 coverage(in_image, out_image, num_samples, rotation_matrix) tells which output
-pixels the source image can see (device tensors).
+pixels the source image can see (device tensors), and
+compose(in_images, out_image, interpolation, rotation_matrices, mode) renders
+several source images into one output (device tensors).
 
 The directory name contains a hyphen (it is the name the build contract fixes);
 import it with importlib.import_module("image-lens-reproject_amd").
@@ -60,6 +62,15 @@ class Status(enum.IntEnum):
     HIP = 8
     OOM = 9
     BAD_ARG = 10
+
+
+class ComposeMode(enum.IntEnum):  # include/lrp.h lrp_compose_mode
+    FIRST = 0
+    MEAN = 1
+    FEATHER = 2
+
+
+COMPOSE_MAX_SOURCES = 8  # include/lrp.h LRP_COMPOSE_MAX_SOURCES
 
 
 class LrpError(RuntimeError):
@@ -308,6 +319,47 @@ def coverage(in_image, out_image, num_samples, rotation_matrix=None, out=None, m
     del keep
     _check(st)
     return out
+
+
+def compose(in_images, out_image, interpolation, rotation_matrices=None, mode=ComposeMode.FIRST, post=None, count=None, device=None,
+            stream=None):
+    """lrp_compose_device (include/lrp.h "compose"): up to COMPOSE_MAX_SOURCES source images of one source mode, each with its
+    own lens parameters, size and rotation (rotation_matrices: one 3 x 3 matrix per source, or None), rendered into out_image by
+    one launch — per output pixel only the sources that cover it (the coverage definition) are sampled, and `mode` says what
+    becomes of them: the first one, their mean, or the mean weighted by the distance to the source's edge.  A pixel no source
+    covers becomes +0.0.  Device tensors only; asynchronous on `stream`.  count: None, True (returns a new (height, width)
+    uint8 CUDA tensor of the number of covering sources per pixel) or such a tensor to fill (returned)."""
+    lib = _native.load()
+    n = len(in_images)
+    want_count = count is not None and count is not False
+    if want_count and count is not True:
+        import torch
+
+        if (not _is_torch(count) or count.dtype != torch.uint8 or not count.is_cuda or not count.is_contiguous()
+                or count.numel() != out_image.height * out_image.width):
+            raise ValueError("count must be a contiguous uint8 CUDA tensor with height*width elements")
+    if not out_image.on_device() or not all(i.on_device() for i in in_images):
+        raise ValueError("compose() takes device tensors only: the data of every input image and of the output must be a CUDA tensor")
+    if device is None:
+        device = out_image.data.device.index
+    plane = None
+    if want_count:
+        import torch
+
+        plane = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}") if count is True else count
+    arr = (LrpImage * max(n, 1))(*[i.to_c() for i in in_images])
+    cout = out_image.to_c()
+    rot, keep = None, None
+    if rotation_matrices is not None:
+        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
+        rot = keep.ctypes.data
+    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    st = lib.lrp_compose_device(arr, n, rot, ctypes.byref(cout), int(interpolation), int(mode),
+                                ctypes.byref(cpost) if cpost is not None else None, plane.data_ptr() if plane is not None else None,
+                                device, _stream_handle(stream))
+    del keep
+    _check(st)
+    return plane
 
 
 def reproject_multi(in_image, out_images, num_samples, interpolation, rotation_matrices=None, post=None, device=None,

@@ -2,7 +2,7 @@
 // reference's dispatch order, kernel-argument construction, device buffers,
 // streams and the batch context.  Host code only; the kernels live in the
 // lrp_kernels_*.hip / lrp_tile_*.hip / lrp_eqs_*.hip / lrp_stg_*.hip (reprojection), lrp_tables.hip, lrp_geo_lists.hip,
-// lrp_coverage.hip (coverage planes), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
+// lrp_coverage.hip (coverage planes), lrp_compose*.hip (compose), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/lrp.h"
+#include "lrp_compose.h"
 #include "lrp_geocache.h"
 #include "lrp_params.h"
 #include "lrp_plan.h"
@@ -42,6 +43,8 @@ hipError_t launch_corner_fill(const KParams &P, hipStream_t stream);
 // lrp_coverage.hip.  A weak reference: the host-code test drivers (tests/native/multi_driver.cpp) link this file against stand-ins
 // of the launchers they exercise; where the unit is not linked in, a coverage request fails (enqueue_coverage).
 __attribute__((weak)) hipError_t launch_coverage(KParams P, int out_lens, int in_mode, uint8_t *plane, int mask_image, int alpha_channel, hipStream_t stream);
+// lrp_compose.hip, weak like launch_coverage (enqueue_compose).
+__attribute__((weak)) hipError_t launch_compose(const ComposeParams &P, int out_lens, int in_mode, int interpolation, hipStream_t stream);
 hipError_t launch_post_process(float *data, uint32_t n_pixels, int channels, float exposure, float reinhard,
                                hipStream_t stream);
 hipError_t launch_synth_fill(float *data, uint32_t n_elems, int channels, uint32_t seed, int depth_channel,
@@ -535,6 +538,69 @@ int enqueue_coverage(const lrp_image *in, const lrp_image *out, int num_samples,
   return LRP_OK;
 }
 
+const char *in_mode_name(int mode) {
+  switch (mode) {
+  case lrp::kInRect: return "rectilinear";
+  case lrp::kInEquidistant: return "equidistant";
+  case lrp::kInEquirect: return "clamped equirectangular";
+  case lrp::kInEquirectLoop: return "wrapping equirectangular";
+  case lrp::kInEquisolid: return "equisolid";
+  default: return "stereographic";
+  }
+}
+
+// lrp_compose_device's checks, in the order include/lrp.h states.
+int validate_compose(const lrp_image *ins, int n_in, const lrp_image *out, int interpolation, int mode) {
+  if (n_in < 1 || n_in > LRP_COMPOSE_MAX_SOURCES)
+    return fail(LRP_ERR_BAD_ARG, "n_in of a compose call must be 1 .. " + std::to_string(LRP_COMPOSE_MAX_SOURCES));
+  if (mode != LRP_COMPOSE_FIRST && mode != LRP_COMPOSE_MEAN && mode != LRP_COMPOSE_FEATHER) return fail(LRP_ERR_BAD_ARG, "unknown compose mode");
+  if (!ins || !out) return fail(LRP_ERR_NULL, "null image");
+  for (int i = 0; i < n_in; ++i) { // (in->channels == out->channels is one of validate()'s checks)
+    const int st = validate(ins + i, out, interpolation, true);
+    if (st != LRP_OK) return st;
+  }
+  const int first = in_lens_mode(ins[0].lens);
+  for (int i = 1; i < n_in; ++i)
+    if (in_lens_mode(ins[i].lens) != first)
+      return fail(LRP_ERR_BAD_ARG, std::string("the sources of a compose call must be of one source mode: source 0 is ") + in_mode_name(first) + ", source " +
+                                       std::to_string(i) + " is " + in_mode_name(in_lens_mode(ins[i].lens)));
+  return LRP_OK;
+}
+
+// One launch of the compose kernel per group of 8 channels (lrp_compose.hip); no table, no geometry-cache entry, no allocation.
+int enqueue_compose(const lrp_image *ins, int n_in, const float *rotations, const lrp_image *out, int interpolation, int mode,
+                    const lrp_post *post, uint8_t *count, hipStream_t stream) {
+  if (!lrp::launch_compose) return fail(LRP_ERR_HIP, "the compose kernels (lrp_compose.hip) are not part of this build");
+  lrp::ComposeParams C;
+  std::memset(&C, 0, sizeof(C));
+  for (int i = 0; i < n_in; ++i) { // the per-source values as make_params() packs them for a reprojection of source i
+    const lrp::KParams P = make_params(ins + i, out, 1, rotations ? rotations + 9 * i : nullptr, post);
+    if (i == 0) {
+      C.out_w = P.out_w, C.out_h = P.out_h, C.channels = P.channels;
+      C.out_lens = P.out_lens;
+      C.exposure = P.exposure, C.reinhard = P.reinhard;
+    }
+    lrp::ComposeSource &S = C.src[i];
+    S.in_w = P.in_w, S.in_h = P.in_h;
+    S.lens = P.in_lens;
+    S.has_rot = P.has_rot;
+    std::memcpy(S.rot, P.rot, sizeof(S.rot));
+  }
+  C.n_src = n_in;
+  C.mode = mode;
+  const int channels = out->channels, group = lrp::kComposeMaxChannels;
+  for (int c0 = 0; c0 < channels; c0 += group) {
+    for (int i = 0; i < n_in; ++i) C.src[i].data = ins[i].data + c0;
+    C.dst = out->data + c0;
+    C.ch_count = std::min(group, channels - c0);
+    C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
+    C.count = c0 == 0 ? count : nullptr;
+    const hipError_t e = lrp::launch_compose(C, out->lens.type, in_lens_mode(ins[0].lens), interpolation, stream);
+    if (e != hipSuccess) return hip_fail(e, "compose kernel launch");
+  }
+  return LRP_OK;
+}
+
 // Grow-only device / pinned buffer.
 struct Buffer {
   void *ptr = nullptr;
@@ -696,6 +762,15 @@ int lrp_coverage_device(const lrp_image *in, const lrp_image *out, int num_sampl
   st = select_device(device);
   if (st != LRP_OK) return st;
   return enqueue_coverage(in, out, num_samples, rotation, coverage, mask_image, alpha_channel, (hipStream_t)stream);
+}
+
+int lrp_compose_device(const lrp_image *ins, int n_in, const float *rotations, const lrp_image *out, int interpolation, int mode,
+                       const lrp_post *post, uint8_t *count, int device, void *stream) {
+  int st = validate_compose(ins, n_in, out, interpolation, mode);
+  if (st != LRP_OK) return st;
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_compose(ins, n_in, rotations, out, interpolation, mode, post, count, (hipStream_t)stream);
 }
 
 namespace {

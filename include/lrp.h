@@ -284,6 +284,44 @@ int lrp_reproject_batch_device(const lrp_image *ins, lrp_image *outs, int n, int
 int lrp_coverage_device(const lrp_image *in, const lrp_image *out, int num_samples, const float *rotation,
                         uint8_t *coverage, int mask_image, int alpha_channel, int device, void *stream);
 
+/* ---- compose: several source images into one output ------------------------------------ */
+
+/* The opposite direction of lrp_reproject_multi_device: n_in device-resident sources (six cube faces, the two fisheyes of a
+ * 360-degree camera, a rig of overlapping cameras), each with its own lens parameters, size and rotation, rendered into ONE
+ * output by one kernel launch (per group of 8 channels).  Per output pixel the target ray is computed once, each source is
+ * asked in turn whether it recorded that ray — the coverage definition above — and only the sources that did are sampled.
+ *
+ * Definition.  num_samples is 1.  All arithmetic is binary32, un-fused, in the order written; min(a, b) is (b < a) ? b : a.
+ * For output pixel (x, y) and source i: vx, vy, vz is the pixel's target ray after rotation i (rotations + 9 * i; the rotation
+ * and the operations of lrp_reproject_device(ins + i, out, 1, ..., rotations + 9 * i); rotations == NULL: no source is rotated,
+ * no multiplication happens), sx, sy the coordinates that source's sampler would receive.  Source i COVERS the pixel iff that
+ * sub-sample is covered under the coverage definition above (front && in_x && in_y, comparisons with NaN false).
+ * s_i is the texel sample<interpolation> returns for (sx, sy) in source i: bit for bit what lrp_reproject_device stores for the
+ * pixel before any post.  k is the number of covering sources.
+ *   LRP_COMPOSE_FIRST    the pixel is s_i of the lowest-numbered covering source;
+ *   LRP_COMPOSE_MEAN     acc_c = +0.0f; for ascending covering i: acc_c = acc_c + s_i,c; the pixel is acc_c / (float)k;
+ *   LRP_COMPOSE_FEATHER  dy = min(sy + 0.5f, ((float)in_h - 0.5f) - sy); dx likewise from sx and in_w (the distance, in texels, to
+ *                        the nearer edge of source i); m = dy for a wrapping equirectangular source, else m = min(dx, dy);
+ *                        w_i = (m < 0x1p-10f) ? 0x1p-10f : m; acc_c = +0.0f, W = +0.0f; for ascending covering i:
+ *                        acc_c = acc_c + w_i * s_i,c (multiply, then add), W = W + w_i; the pixel is acc_c / W.
+ * A pixel no source covers (k == 0) becomes +0.0f in every channel.  post: the reference's tonemap on the first min(C, 3)
+ * channels of the composed value, as in every other entry point; a k == 0 pixel stays +0.0f in every channel whatever post is.
+ * count: a device pointer of any alignment, or NULL: receives k per pixel, out->width * out->height bytes, row-major, unpadded.
+ *
+ * Asynchronous on `stream`; allocates nothing, does not synchronise, builds no lens table, neither reads nor writes the geometry
+ * cache (the lrp_geometry_cache_stats counters do not move).
+ * Errors, all before a device is touched, in this order: n_in outside 1 .. LRP_COMPOSE_MAX_SOURCES or an unknown mode:
+ * LRP_ERR_BAD_ARG; ins or out NULL: LRP_ERR_NULL; per source, in ascending order, the checks of lrp_reproject_device(ins + i, out)
+ * with its statuses (lens and extension bits, interpolation, channels — every source has out->channels channels, else
+ * LRP_ERR_CHANNELS —, sizes, data pointers); then all sources must resolve to the same source mode — rectilinear, equidistant,
+ * clamped equirectangular, wrapping equirectangular (a full turn of longitude), equisolid, stereographic —, else LRP_ERR_BAD_ARG
+ * with an lrp_last_error text that names the two modes.  Sizes, lens parameters and rotations may differ per source. */
+#define LRP_COMPOSE_MAX_SOURCES 8
+typedef enum lrp_compose_mode { LRP_COMPOSE_FIRST = 0, LRP_COMPOSE_MEAN = 1, LRP_COMPOSE_FEATHER = 2 } lrp_compose_mode;
+int lrp_compose_device(const lrp_image *ins, int n_in, const float *rotations /* n_in x 9, or NULL */, const lrp_image *out,
+                       int interpolation, int mode, const lrp_post *post, uint8_t *count /* out->width * out->height bytes, or NULL */,
+                       int device, void *stream);
+
 /* ---- one source, several outputs, several GPUs (BASELINE configs[4]) ---------- */
 
 /* One host source, n_out host outputs (lenses in outs[i].lens, rotations + 9 * i or none): the
