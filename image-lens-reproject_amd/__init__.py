@@ -617,6 +617,42 @@ def encode_pixels(src, dst, dst_format, fill=0, stream=None):
                                         int(fill), n, src.device.index, _stream_handle(stream)))
 
 
+def reproject_packed(in_image, in_format, in_data, out_image, out_format, out_data, out_fill, num_samples, interpolation,
+                     rotation_matrix=None, post=None, device=None, stream=None):
+    """lrp_reproject_packed_device (include/lrp.h "packed pixels"): BatchContext.submit_packed's decode, reproject and encode as
+    one launch on the device.  `in_data` / `out_data` are contiguous CUDA tensors of shape (height, width, packed_channels) in
+    the file formats — uint8, int16 (half bits) / float16, float32 (output only), as decode_pixels takes them; the images
+    describe the float geometry (their own data is not looked at).  The output bytes are those of decode_pixels -> reproject
+    -> encode_pixels.  Asynchronous on `stream` (default: torch's current stream)."""
+    lib = _native.load()
+    for name, t in (("in_data", in_data), ("out_data", out_data)):
+        if not _is_torch(t) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"reproject_packed() takes device tensors only: {name} must be a contiguous CUDA tensor")
+    # the kernel addresses the tensors by the format's sample size: a tensor of narrower elements would be read or written
+    # past its end (an unknown format is left to the library's own LRP_ERR_BAD_ARG)
+    sample_bytes = {int(PixelFormat.F32): 4, int(PixelFormat.F16): 2, int(PixelFormat.U8_GAMMA): 1}
+    for name, t, fmt in (("in_data", in_data, int(in_format)), ("out_data", out_data, int(out_format))):
+        if fmt in sample_bytes and t.element_size() != sample_bytes[fmt]:
+            raise ValueError(f"{name}: elements of {t.element_size()} bytes ({t.dtype}) for a format of {sample_bytes[fmt]}-byte samples")
+    if (in_data.numel() != in_image.width * in_image.height * in_data.shape[-1]
+            or out_data.numel() != out_image.width * out_image.height * out_data.shape[-1]):
+        raise ValueError("packed tensors must hold height*width pixels of shape[-1] samples")
+    cin, cout = LrpImage(), LrpImage()
+    for c, im, t in ((cin, in_image, in_data), (cout, out_image, out_data)):
+        c.lens = im.lens.to_c()
+        c.width, c.height, c.channels = im.width, im.height, im.channels
+        c.data = t.data_ptr()
+        c.data_layout = im.data_layout
+    keep, rot = _rotation_arg(rotation_matrix)
+    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    dev = in_data.device.index if device is None else device
+    st = lib.lrp_reproject_packed_device(ctypes.byref(cin), int(in_format), int(in_data.shape[-1]), ctypes.byref(cout), int(out_format),
+                                         int(out_data.shape[-1]), int(out_fill), int(num_samples), int(interpolation), rot,
+                                         ctypes.byref(cpost) if cpost is not None else None, dev, _stream_handle(stream))
+    del keep
+    _check(st)
+
+
 def pixel_tables():
     """(decode[256], threshold[256]) of LRP_PIXEL_U8_GAMMA as the host's powf made them."""
     dec = (ctypes.c_float * 256)()

@@ -2,7 +2,7 @@
 // reference's dispatch order, kernel-argument construction, device buffers,
 // streams and the batch context.  Host code only; the kernels live in the
 // lrp_kernels_*.hip / lrp_tile_*.hip / lrp_eqs_*.hip / lrp_stg_*.hip (reprojection), lrp_tables.hip, lrp_geo_lists.hip,
-// lrp_coverage.hip (coverage planes), lrp_compose*.hip (compose), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
+// lrp_coverage.hip (coverage planes), lrp_compose*.hip (compose), lrp_packed*.hip (packed pixels), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +23,7 @@
 #include "../../include/lrp.h"
 #include "lrp_compose.h"
 #include "lrp_geocache.h"
+#include "lrp_packed.h"
 #include "lrp_params.h"
 #include "lrp_plan.h"
 #include "lrp_tables.h"
@@ -45,6 +46,8 @@ hipError_t launch_corner_fill(const KParams &P, hipStream_t stream);
 __attribute__((weak)) hipError_t launch_coverage(KParams P, int out_lens, int in_mode, uint8_t *plane, int mask_image, int alpha_channel, hipStream_t stream);
 // lrp_compose.hip, weak like launch_coverage (enqueue_compose).
 __attribute__((weak)) hipError_t launch_compose(const ComposeParams &P, int out_lens, int in_mode, int interpolation, hipStream_t stream);
+// lrp_packed.hip, weak like launch_coverage (enqueue_packed).
+__attribute__((weak)) hipError_t launch_packed(PackedParams P, int in_format, int out_lens, int in_mode, int interpolation, int device, hipStream_t stream);
 hipError_t launch_post_process(float *data, uint32_t n_pixels, int channels, float exposure, float reinhard,
                                hipStream_t stream);
 hipError_t launch_synth_fill(float *data, uint32_t n_elems, int channels, uint32_t seed, int depth_channel,
@@ -601,6 +604,79 @@ int enqueue_compose(const lrp_image *ins, int n_in, const float *rotations, cons
   return LRP_OK;
 }
 
+static_assert((int)lrp::kPackedF32 == LRP_PIXEL_F32 && (int)lrp::kPackedF16 == LRP_PIXEL_F16 && (int)lrp::kPackedU8 == LRP_PIXEL_U8_GAMMA, "lrp_packed.h numbers pixel formats like include/lrp.h");
+
+bool format_ok(int f) { return f == LRP_PIXEL_F32 || f == LRP_PIXEL_F16 || f == LRP_PIXEL_U8_GAMMA; }
+
+// The packed image of `packed_channels` samples per pixel fits the byte offsets of the packed kernel (32-bit): the size limit of
+// validate() — 2^31 — applied to bytes.  (Dimensions are positive: validate() ran.)
+bool packed_addressable(const lrp_image &im, int format, int packed_channels) {
+  const unsigned long long px = (unsigned long long)im.width * (unsigned long long)im.height; // < 2^62
+  const unsigned long long sample = lrp::pixel_bytes(format, 1);
+  return px <= kMaxImageFloats / sample && (unsigned long long)packed_channels <= kMaxImageFloats / (px * sample);
+}
+
+// lrp_reproject_packed_device's checks, in the order include/lrp.h states.
+int validate_packed(const lrp_image *in, int in_format, int in_pch, const lrp_image *out, int out_format, int out_pch, int interpolation) {
+  const int st = validate(in, out, interpolation, true);
+  if (st != LRP_OK) return st;
+  if (in_format == LRP_PIXEL_F32)
+    return fail(LRP_ERR_BAD_ARG, "a float32 source needs no decode: call lrp_reproject_device + lrp_encode_pixels_device");
+  if (!format_ok(in_format) || !format_ok(out_format)) return fail(LRP_ERR_BAD_ARG, "unknown pixel format");
+  if (in_pch < 1 || out_pch < 1) return fail(LRP_ERR_BAD_ARG, "packed channel counts must be >= 1");
+  if (in->channels > lrp::kPackedMaxChannels)
+    return fail(LRP_ERR_CHANNELS, "lrp_reproject_packed_device renders at most " + std::to_string(lrp::kPackedMaxChannels) + " channels");
+  if (!packed_addressable(*in, in_format, in_pch) || !packed_addressable(*out, out_format, out_pch))
+    return fail(LRP_ERR_BAD_DIMS, "a packed image of more than 2^31 bytes cannot be addressed (the packed kernel forms 32-bit byte offsets)");
+  return LRP_OK;
+}
+
+// One launch of the packed kernel (lrp_packed.hip).  num_samples == 1: through the geometry cache, under the key
+// enqueue_reproject builds for this geometry — the entry is shared with lrp_reproject_device in both directions.
+int enqueue_packed(const lrp_image *in, int in_format, int in_pch, lrp_image *out, int out_format, int out_pch, unsigned out_fill,
+                   int num_samples, int interpolation, const float *rotation, const lrp_post *post, int device, hipStream_t stream) {
+  if (num_samples <= 0) return LRP_OK; // reference loop body never runs: output untouched
+  if (!lrp::launch_packed) return fail(LRP_ERR_HIP, "the packed-pixel kernels (lrp_packed.hip) are not part of this build");
+  const lrp::KParams K = make_params(in, out, num_samples, rotation, post);
+  lrp::PackedParams P;
+  std::memset(&P, 0, sizeof(P));
+  P.src = in->data, P.dst = out->data;
+  P.in_w = K.in_w, P.in_h = K.in_h, P.out_w = K.out_w, P.out_h = K.out_h;
+  P.channels = K.channels;
+  P.in_channels = in_pch, P.out_channels = out_pch;
+  P.out_format = out_format;
+  P.out_fill = out_fill;
+  P.num_samples = K.num_samples;
+  P.normalize = K.normalize;
+  P.in_lens = K.in_lens, P.out_lens = K.out_lens;
+  std::memcpy(P.rot, K.rot, sizeof(P.rot));
+  P.has_rot = K.has_rot, P.has_post = K.has_post;
+  P.exposure = K.exposure, P.reinhard = K.reinhard;
+  const int ol = out->lens.type, im = in_lens_mode(in->lens);
+  lrp::GeoUse geo;
+  if (num_samples == 1 && knob(kKnobGeoCache) != 0) {
+    lrp::GeoKey key;
+    std::memset(&key, 0, sizeof(key));
+    key.device = device;
+    key.out_type = ol;
+    key.in_mode = im;
+    key.out_w = out->width, key.out_h = out->height, key.in_w = in->width, key.in_h = in->height;
+    key.has_rot = P.has_rot;
+    key.num_samples = num_samples;
+    key.out_lens = lrp::geo_canonical_lens(P.out_lens, out->lens.type), key.in_lens = lrp::geo_canonical_lens(P.in_lens, in->lens.type);
+    if (P.has_rot) std::memcpy(key.rot, P.rot, sizeof(key.rot));
+    lrp::geo_acquire(key, /*want_boxes=*/false, stream, &geo);
+    if (geo.mode == 1 || geo.mode == 2) {
+      P.geo_mode = geo.mode;
+      P.geo_xy = geo.xy;
+    }
+  }
+  const hipError_t e = lrp::launch_packed(P, in_format, ol, im, interpolation, device, stream);
+  lrp::geo_launched(&geo, stream, e == hipSuccess);
+  if (e != hipSuccess) return hip_fail(e, "packed-pixel kernel launch");
+  return LRP_OK;
+}
+
 // Grow-only device / pinned buffer.
 struct Buffer {
   void *ptr = nullptr;
@@ -771,6 +847,17 @@ int lrp_compose_device(const lrp_image *ins, int n_in, const float *rotations, c
   st = select_device(device);
   if (st != LRP_OK) return st;
   return enqueue_compose(ins, n_in, rotations, out, interpolation, mode, post, count, (hipStream_t)stream);
+}
+
+int lrp_reproject_packed_device(const lrp_image *in, int in_format, int in_packed_channels, lrp_image *out, int out_format,
+                                int out_packed_channels, unsigned out_fill, int num_samples, int interpolation, const float *rotation,
+                                const lrp_post *post, int device, void *stream) {
+  int st = validate_packed(in, in_format, in_packed_channels, out, out_format, out_packed_channels, interpolation);
+  if (st != LRP_OK) return st;
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_packed(in, in_format, in_packed_channels, out, out_format, out_packed_channels, out_fill, num_samples, interpolation,
+                        rotation, post, device, (hipStream_t)stream);
 }
 
 namespace {
@@ -1097,8 +1184,6 @@ void lrp_context_destroy(lrp_context *ctx) {
 }
 
 namespace {
-bool format_ok(int f) { return f == LRP_PIXEL_F32 || f == LRP_PIXEL_F16 || f == LRP_PIXEL_U8_GAMMA; }
-
 // One image through the three-stage pipeline.  Formats LRP_PIXEL_F32 with packed channels == image
 // channels: the host buffers are the kernels' own layout and are copied straight into / out of the
 // slot's float buffers; otherwise the frame is uploaded as it is and converted on the device.

@@ -253,6 +253,15 @@ template <int CH> __device__ __forceinline__ void store_texel(float *__restrict_
 
 template <int CH> constexpr int texel_lanes() { return CH == 0 ? kMaxDynChannels : CH; }
 
+// How a sampler fetches a tap: the policy object the samplers below take last (defaulted).  FloatTaps is the interleaved
+// float32 source every render kernel reads — load_texel, nothing else; a kernel whose source has another format hands the
+// samplers a loader of its own (lrp_packed_kernel.h) and shares their index and blend arithmetic.
+struct FloatTaps {
+  template <int CH> __device__ __forceinline__ Texel<CH> load(const float *__restrict__ src, uint32_t elem_off, int ch) const {
+    return load_texel<CH>(src, elem_off, ch);
+  }
+};
+
 // cubicInterpolate (src/reproject.cpp:92-98) in the reference's association
 // order; `half_t` is 0.5f * t (computed once per axis: same bits).
 __device__ __forceinline__ float catmull_rom(float a, float b, float c, float d, float t, float half_t) {
@@ -265,17 +274,17 @@ __device__ __forceinline__ float catmull_rom(float a, float b, float c, float d,
 // ---- samplers ---------------------------------------------------------------
 
 // sample_nearest, src/reproject.cpp:39-53
-template <int CH, bool Loop>
-__device__ __forceinline__ Texel<CH> sample_nearest(const KParams &P, float sx, float sy) {
+template <int CH, bool Loop, class Taps = FloatTaps>
+__device__ __forceinline__ Texel<CH> sample_nearest(const KParams &P, float sx, float sy, const Taps taps = Taps()) {
   const int lx = column<Loop>(trunc_x86(sx + 0.5f), P.in_w);
   const int ly = clamp_index(trunc_x86(sy + 0.5f), P.in_h - 1);
   const uint32_t off = ((uint32_t)ly * (uint32_t)P.in_w + (uint32_t)lx) * (uint32_t)P.channels;
-  return load_texel<CH>(P.src, off, P.ch_count);
+  return taps.template load<CH>(P.src, off, P.ch_count);
 }
 
 // sample_bilinear, src/reproject.cpp:55-90
-template <int CH, bool Loop>
-__device__ __forceinline__ Texel<CH> sample_bilinear(const KParams &P, float sx, float sy) {
+template <int CH, bool Loop, class Taps = FloatTaps>
+__device__ __forceinline__ Texel<CH> sample_bilinear(const KParams &P, float sx, float sy, const Taps taps = Taps()) {
   const int w = P.in_w, h = P.in_h, C = P.channels;
   const int lx = column<Loop>(trunc_x86(sx), w);
   const int ux = column<Loop>(trunc_x86(sx + 1.0f), w);
@@ -286,10 +295,10 @@ __device__ __forceinline__ Texel<CH> sample_bilinear(const KParams &P, float sx,
   const float cfx = 1.0f - fx;
   const float cfy = 1.0f - fy;
   const uint32_t row_l = (uint32_t)ly * (uint32_t)w, row_u = (uint32_t)uy * (uint32_t)w;
-  const Texel<CH> ll = load_texel<CH>(P.src, (row_l + lx) * C, P.ch_count);
-  const Texel<CH> lu = load_texel<CH>(P.src, (row_l + ux) * C, P.ch_count);
-  const Texel<CH> ul = load_texel<CH>(P.src, (row_u + lx) * C, P.ch_count);
-  const Texel<CH> uu = load_texel<CH>(P.src, (row_u + ux) * C, P.ch_count);
+  const Texel<CH> ll = taps.template load<CH>(P.src, (row_l + lx) * C, P.ch_count);
+  const Texel<CH> lu = taps.template load<CH>(P.src, (row_l + ux) * C, P.ch_count);
+  const Texel<CH> ul = taps.template load<CH>(P.src, (row_u + lx) * C, P.ch_count);
+  const Texel<CH> uu = taps.template load<CH>(P.src, (row_u + ux) * C, P.ch_count);
   Texel<CH> r;
 #pragma unroll
   for (int c = 0; c < texel_lanes<CH>(); ++c) {
@@ -302,8 +311,8 @@ __device__ __forceinline__ Texel<CH> sample_bilinear(const KParams &P, float sx,
 
 // sample_bicubic + bicubicInterpolate, src/reproject.cpp:100-148: vertical
 // cubic per tap column, then the horizontal cubic.
-template <int CH, bool Loop>
-__device__ __forceinline__ Texel<CH> sample_bicubic(const KParams &P, float sx, float sy) {
+template <int CH, bool Loop, class Taps = FloatTaps>
+__device__ __forceinline__ Texel<CH> sample_bicubic(const KParams &P, float sx, float sy, const Taps taps = Taps()) {
   const int w = P.in_w, h = P.in_h, C = P.channels;
   int xs[4], ys[4];
   xs[0] = column<Loop>(trunc_x86(sx - 1.0f), w);
@@ -323,10 +332,10 @@ __device__ __forceinline__ Texel<CH> sample_bicubic(const KParams &P, float sx, 
   Texel<CH> col[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const Texel<CH> p0 = load_texel<CH>(P.src, (rows[0] + xs[i]) * C, P.ch_count);
-    const Texel<CH> p1 = load_texel<CH>(P.src, (rows[1] + xs[i]) * C, P.ch_count);
-    const Texel<CH> p2 = load_texel<CH>(P.src, (rows[2] + xs[i]) * C, P.ch_count);
-    const Texel<CH> p3 = load_texel<CH>(P.src, (rows[3] + xs[i]) * C, P.ch_count);
+    const Texel<CH> p0 = taps.template load<CH>(P.src, (rows[0] + xs[i]) * C, P.ch_count);
+    const Texel<CH> p1 = taps.template load<CH>(P.src, (rows[1] + xs[i]) * C, P.ch_count);
+    const Texel<CH> p2 = taps.template load<CH>(P.src, (rows[2] + xs[i]) * C, P.ch_count);
+    const Texel<CH> p3 = taps.template load<CH>(P.src, (rows[3] + xs[i]) * C, P.ch_count);
 #pragma unroll
     for (int c = 0; c < texel_lanes<CH>(); ++c)
       col[i].v[c] = catmull_rom(p0.v[c], p1.v[c], p2.v[c], p3.v[c], fy, hfy);
@@ -338,14 +347,14 @@ __device__ __forceinline__ Texel<CH> sample_bicubic(const KParams &P, float sx, 
   return r;
 }
 
-template <int Interp, int CH, bool Loop>
-__device__ __forceinline__ Texel<CH> sample(const KParams &P, float sx, float sy) {
+template <int Interp, int CH, bool Loop, class Taps = FloatTaps>
+__device__ __forceinline__ Texel<CH> sample(const KParams &P, float sx, float sy, const Taps taps = Taps()) {
   if constexpr (Interp == 0)
-    return sample_nearest<CH, Loop>(P, sx, sy);
+    return sample_nearest<CH, Loop>(P, sx, sy, taps);
   else if constexpr (Interp == 1)
-    return sample_bilinear<CH, Loop>(P, sx, sy);
+    return sample_bilinear<CH, Loop>(P, sx, sy, taps);
   else
-    return sample_bicubic<CH, Loop>(P, sx, sy);
+    return sample_bicubic<CH, Loop>(P, sx, sy, taps);
 }
 
 // post_process on one value (src/reproject.cpp:428-431)

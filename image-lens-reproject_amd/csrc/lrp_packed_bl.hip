@@ -1,0 +1,12 @@
+// lrp_packed_bl.hip — the bilinear instantiations of the packed-pixel kernel (lrp_packed_kernel.h; launcher: lrp_packed.hip).
+#include <hip/hip_runtime.h>
+
+#include "lrp_packed_kernel.h"
+
+namespace lrp {
+
+hipError_t launch_packed_bilinear(const PackedParams &P, int in_format, int out_lens, int in_mode, hipStream_t stream) {
+  return launch_packed_interp<1>(P, in_format, out_lens, in_mode, stream);
+}
+
+} // namespace lrp

@@ -191,6 +191,17 @@ hipError_t launch_encode_pixels(const float *src, int src_channels, void *dst, i
   return hipGetLastError();
 }
 
+// The device copies of the two tables (256 floats each) for a kernel of another unit (lrp_packed.hip); uploaded on first use
+// like the conversion kernels' own.
+hipError_t pixel_tables_device(int device, hipStream_t stream, const float **decode, const float **threshold) {
+  const PixelTables *t = nullptr;
+  const hipError_t e = device_tables(device, stream, &t);
+  if (e != hipSuccess) return e;
+  *decode = t->decode;
+  *threshold = t->threshold;
+  return hipSuccess;
+}
+
 // Host copies of the two tables (tests, and the CLI's own host-side quantiser check).
 void pixel_tables_host(float decode[256], float threshold[256]) {
   const PixelTables &t = host_tables();

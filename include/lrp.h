@@ -407,6 +407,48 @@ int lrp_context_submit_packed(lrp_context *ctx, const lrp_image *in, int in_form
                               int *ticket);
 int lrp_context_wait_ticket(lrp_context *ctx, int ticket);
 
+/* ---- packed pixels: 8-bit and half images reprojected on the device by one launch -------- */
+
+/* lrp_context_submit_packed's three kernels — decode, reproject, encode — as ONE launch on device-resident packed buffers: for a
+ * caller whose frames already sit on the GPU in their real format (RGBA8 from a video decoder, binary16 from an EXR reader).
+ * No float32 staging image exists: a pixel's taps are decoded as they are loaded and its value is encoded as it is stored.
+ * in->data / out->data are device pointers to packed samples of any alignment, with the meaning lrp_context_submit_packed
+ * gives its host pointers: in->width x in->height texels of in_packed_channels samples in in_format, out->width x out->height
+ * pixels of out_packed_channels samples in out_format.  C = in->channels = out->channels (at most 8) is the channel count of
+ * the float image the kernels of the chain would see.
+ *
+ * Definition.  The bytes written to out->data are exactly those of this chain with two float32 temporaries tmp_in, tmp_out of C
+ * channels:
+ *   lrp_decode_pixels_device(in->data, in_format, in_packed_channels, tmp_in, C, ...)
+ *   lrp_reproject_device(tmp_in -> tmp_out, num_samples, interpolation, rotation, post)
+ *   lrp_encode_pixels_device(tmp_out, C, out->data, out_format, out_packed_channels, out_fill, ...)
+ * corner cases included: the channels of the source beyond in_packed_channels are +0.0f taps that go through the sampler's
+ * arithmetic; packed source samples beyond C are not read; output samples beyond C are out_fill (the low 8 / 16 bits; for
+ * LRP_PIXEL_F32 the fill's bit pattern); the 8-bit encode clamps with std::max(0.0f, std::min(1.0f, v)) in libstdc++'s
+ * comparison direction — NaN becomes 255, -0 becomes 0 —; num_samples <= 0 leaves out->data untouched.  Nothing new is
+ * defined about arithmetic: the 8-bit decode is the 256-entry table and the encode the search of the 255 thresholds of
+ * lrp_pixel_tables, the half conversions are include/lrp_half.h.  One thing the chain leaves open is settled here: where a
+ * sample of the chain is a NaN (a NaN or an infinity among the taps), its sign and payload are those of the chain whose
+ * lrp_reproject_device renders with the one-pixel-per-lane kernels (lrp_debug_kernel(0)) — the samplers this call runs.
+ * The kernel families of lrp_reproject_device agree among themselves on every bit but these (their blends associate
+ * differently and a NaN keeps the sign of the operand it came from); an 8-bit output has no NaN (it is 255).
+ *
+ * in_format is LRP_PIXEL_F16 or LRP_PIXEL_U8_GAMMA (a float32 source needs no decode: lrp_reproject_device +
+ * lrp_encode_pixels_device); out_format is any of the three.
+ *
+ * Asynchronous on `stream`.  The first call on a device uploads the two 8-bit tables (2 KiB, one synchronisation, like the
+ * conversion kernels).  A num_samples == 1 call goes through the geometry cache under the key of lrp_reproject_device for the
+ * same geometry: the first launch writes the coordinate map as a side output, later ones — of either entry point — load it
+ * (lrp_geometry_cache_stats: fills / hits); a capturing stream, a switched-off cache or lrp_debug_set("geo_cache", 0) compute.
+ * Errors, all before a device is touched, in this order: in or out NULL: LRP_ERR_NULL; the checks of lrp_reproject_device in
+ * its order and with its statuses (lens and extension bits, interpolation, channels, sizes, data pointers); LRP_ERR_BAD_ARG
+ * for in_format == LRP_PIXEL_F32, an unknown format or a packed channel count < 1; LRP_ERR_CHANNELS for C > 8;
+ * LRP_ERR_BAD_DIMS for a packed image — width x height x packed channels x bytes per sample — of more than 2^31 bytes (the
+ * kernel forms 32-bit byte offsets). */
+int lrp_reproject_packed_device(const lrp_image *in, int in_format, int in_packed_channels, lrp_image *out, int out_format,
+                                int out_packed_channels, unsigned out_fill, int num_samples, int interpolation,
+                                const float *rotation, const lrp_post *post, int device, void *stream);
+
 /* ---- synthetic frames (bench / tests) -------------------------------------- */
 
 /* Fill a device buffer with the counter-based synthetic frame of SURVEY.md §8d

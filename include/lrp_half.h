@@ -11,12 +11,12 @@
 #include <string.h>
 
 #if defined(__HIPCC__)
-#define LRP_HD __host__ __device__
+#define LRP_HALF_HD __host__ __device__
 #else
-#define LRP_HD
+#define LRP_HALF_HD
 #endif
 
-LRP_HD static inline uint32_t lrp_half_to_float_bits(uint16_t h) {
+LRP_HALF_HD static inline uint32_t lrp_half_to_float_bits(uint16_t h) {
   const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
   uint32_t exp = (h >> 10) & 0x1fu, man = h & 0x3ffu;
   if (exp == 0) {
@@ -32,7 +32,7 @@ LRP_HD static inline uint32_t lrp_half_to_float_bits(uint16_t h) {
   return sign | ((exp + 112u) << 23) | (man << 13);
 }
 
-LRP_HD static inline uint16_t lrp_float_bits_to_half(uint32_t x) {
+LRP_HALF_HD static inline uint16_t lrp_float_bits_to_half(uint32_t x) {
   const uint32_t sign = (x >> 16) & 0x8000u;
   x &= 0x7fffffffu;
   if (x >= 0x7f800000u) { /* inf / NaN: the payload's top ten bits kept, bit 0 set if they are all zero — Imath's
@@ -58,5 +58,7 @@ LRP_HD static inline uint16_t lrp_float_bits_to_half(uint32_t x) {
   if (lost > 0x1000u || (lost == 0x1000u && (m & 1u))) ++m;
   return (uint16_t)(sign | m);
 }
+
+#undef LRP_HALF_HD
 
 #endif /* LRP_HALF_H */
