@@ -31,6 +31,7 @@ const Option kOptions[] = {
     {"nn", 0, false, nullptr, "", "Nearest-neighbour interpolation.", "Sampling"},
     {"bl", 0, false, nullptr, "", "Bilinear interpolation.", "Sampling"},
     {"bc", 0, false, nullptr, "", "Bicubic interpolation (default).", "Sampling"},
+    {"lanczos", 0, false, nullptr, "", "Lanczos-3 interpolation (MI355X addition).", "Sampling"},
     {"scale", 0, true, "1.0", "fraction", "Output size as a fraction of the input size (rounded towards zero); raise --samples when down-scaling.", "Sampling"},
     {"output-resolution", 0, true, nullptr, "width,height", "Fixed output resolution; overrides --scale.", "Sampling"},
     {"i-rectilinear", 0, true, nullptr, "focal_length,sensor_width", "Input images are rectilinear.", "Input optics (with --no-configs)"},

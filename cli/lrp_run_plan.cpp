@@ -176,8 +176,9 @@ int resolve_rendering(const CommandLine &cl, const char *, RunPlan &p) {
 }
 
 int resolve_interpolation(const CommandLine &cl, const char *argv0, RunPlan &p) {
-  // several flags only warn, the last in the order nn, bl, bc wins (src/main.cpp:359-376)
-  static const struct { const char *flag; int value; } kInterp[] = {{"nn", LRP_NEAREST}, {"bl", LRP_BILINEAR}, {"bc", LRP_BICUBIC}};
+  // several flags only warn, the last in the order nn, bl, bc wins (src/main.cpp:359-376); --lanczos (include/lrp.h
+  // "Lanczos-3") takes part as a fourth flag behind bc
+  static const struct { const char *flag; int value; } kInterp[] = {{"nn", LRP_NEAREST}, {"bl", LRP_BILINEAR}, {"bc", LRP_BICUBIC}, {"lanczos", LRP_LANCZOS3}};
   int given = 0;
   for (const auto &i : kInterp)
     if (cl.has(i.flag)) {

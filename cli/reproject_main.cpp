@@ -34,6 +34,7 @@ int main(int argc, char **argv) {
   }
   // the opt-in lens extensions (include/lrp.h)
   lrp_lens_extensions((cl.has("allow-equisolid") ? LRP_LENS_EXT_EQUISOLID : 0) | (cl.has("allow-stereographic") ? LRP_LENS_EXT_STEREOGRAPHIC : 0));
+  if (cl.has("lanczos")) lrp_sampler_extensions(LRP_SAMPLER_EXT_LANCZOS3); // --lanczos switches its extension on by itself
   RunPlan plan;
   if (int rc = resolve_run_plan(cl, argv[0], plan)) return rc;
 

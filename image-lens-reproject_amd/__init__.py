@@ -245,6 +245,16 @@ def lens_extensions(mask=None):
     return _native.load().lrp_lens_extensions(-1 if mask is None else int(mask))
 
 
+LANCZOS3 = 3  # include/lrp.h LRP_LANCZOS3: an interpolation value outside Interpolation (the reference's enum keeps its three members)
+SAMPLER_EXT_LANCZOS3 = 1  # include/lrp.h LRP_SAMPLER_EXT_LANCZOS3
+
+
+def sampler_extensions(mask=None):
+    """lrp_sampler_extensions: the process-wide mask of opt-in sampler extensions (0 by default: interpolation LANCZOS3 is
+    rejected like any unknown value).  Sets the mask and returns the previous one; None only queries."""
+    return _native.load().lrp_sampler_extensions(-1 if mask is None else int(mask))
+
+
 def debug_set(name, value=-1):
     """lrp_debug_set: the named A/B switch ("xsep", "quad", "mirror_modes", "win_edge", "win_split", "geo_cache",
     "batch_frames", "multi_fork", "geo_strip", "geo_big", "geo_lists", "geo_fill_stream", "geo_fill_fused", "kernel"; "listed_launches" is a

@@ -177,6 +177,7 @@ SYMBOLS = {
         [_P(LrpLens), ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float],
     ),
     "lrp_lens_extensions": (ctypes.c_int, [ctypes.c_int]),
+    "lrp_sampler_extensions": (ctypes.c_int, [ctypes.c_int]),
     "lrp_lens_equirectangular": (
         None,
         [_P(LrpLens), ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float],

@@ -2,7 +2,7 @@
 // reference's dispatch order, kernel-argument construction, device buffers,
 // streams and the batch context.  Host code only; the kernels live in the
 // lrp_kernels_*.hip / lrp_tile_*.hip / lrp_eqs_*.hip / lrp_stg_*.hip (reprojection), lrp_tables.hip, lrp_geo_lists.hip,
-// lrp_coverage.hip (coverage planes), lrp_compose*.hip (compose), lrp_packed*.hip (packed pixels), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
+// lrp_coverage.hip (coverage planes), lrp_compose*.hip (compose), lrp_packed*.hip (packed pixels), lrp_lanczos*.hip (the Lanczos-3 sampler), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,6 +48,8 @@ __attribute__((weak)) hipError_t launch_coverage(KParams P, int out_lens, int in
 __attribute__((weak)) hipError_t launch_compose(const ComposeParams &P, int out_lens, int in_mode, int interpolation, hipStream_t stream);
 // lrp_packed.hip, weak like launch_coverage (enqueue_packed).
 __attribute__((weak)) hipError_t launch_packed(PackedParams P, int in_format, int out_lens, int in_mode, int interpolation, int device, hipStream_t stream);
+// lrp_lanczos.hip, weak like launch_coverage (enqueue_lanczos).
+__attribute__((weak)) hipError_t launch_lanczos(KParams P, int out_lens, int in_mode, hipStream_t stream);
 hipError_t launch_post_process(float *data, uint32_t n_pixels, int channels, float exposure, float reinhard,
                                hipStream_t stream);
 hipError_t launch_synth_fill(float *data, uint32_t n_elems, int channels, uint32_t seed, int depth_channel,
@@ -103,6 +105,9 @@ int select_device(int device) {
 // Opt-in lens extensions (lrp_lens_extensions): a mask of LRP_LENS_EXT_*, 0 — the reference's lenses only — by default.
 std::atomic<int> g_lens_ext{0};
 
+// Opt-in sampler extensions (lrp_sampler_extensions): a mask of LRP_SAMPLER_EXT_*, 0 — the reference's samplers only — by default.
+std::atomic<int> g_sampler_ext{0};
+
 // `ext`: the extension mask, read once per call
 bool lens_in_hot_path(int type, int ext) {
   return type == LRP_RECTILINEAR || type == LRP_FISHEYE_EQUIDISTANT || type == LRP_EQUIRECTANGULAR ||
@@ -146,13 +151,15 @@ bool image_fits_byte_offsets(const lrp_image &im) { return (unsigned long long)i
 
 // Checks in the order the reference dispatches: output lens
 // (src/reproject.cpp:408-418), input lens (:378-398), interpolation (:352-367);
-// then the preconditions the reference leaves unchecked.
-int validate(const lrp_image *in, const lrp_image *out, int interpolation, bool need_data) {
+// then the preconditions the reference leaves unchecked.  lanczos_entry: the entry point renders LRP_LANCZOS3 while
+// LRP_SAMPLER_EXT_LANCZOS3 is on (every one that reaches enqueue_reproject; compose and packed pixels do not).
+int validate(const lrp_image *in, const lrp_image *out, int interpolation, bool need_data, bool lanczos_entry) {
   if (!in || !out) return fail(LRP_ERR_NULL, "null image");
   const int ext = g_lens_ext.load(std::memory_order_relaxed);
   if (!lens_in_hot_path(out->lens.type, ext)) return fail(LRP_ERR_OUTPUT_LENS, "Output lens type not supported.");
   if (!lens_in_hot_path(in->lens.type, ext)) return fail(LRP_ERR_INPUT_LENS, "Input lens type not supported.");
-  if (interpolation != LRP_NEAREST && interpolation != LRP_BILINEAR && interpolation != LRP_BICUBIC)
+  const bool lanczos = interpolation == LRP_LANCZOS3 && lanczos_entry && (g_sampler_ext.load(std::memory_order_relaxed) & LRP_SAMPLER_EXT_LANCZOS3) != 0;
+  if (interpolation != LRP_NEAREST && interpolation != LRP_BILINEAR && interpolation != LRP_BICUBIC && !lanczos)
     return fail(LRP_ERR_INTERPOLATION, "Interpolation method not supported.");
   if (in->channels < 1 || in->channels != out->channels)
     return fail(LRP_ERR_CHANNELS, "in->channels must equal out->channels and be >= 1");
@@ -339,6 +346,54 @@ static_assert((int)lrp::kPlanInRect == (int)lrp::kInRect && (int)lrp::kPlanInEqu
               "lrp_plan.h numbers input modes like lrp_params.h");
 static_assert((int)lrp::kPlanNearest == LRP_NEAREST && (int)lrp::kPlanBilinear == LRP_BILINEAR && (int)lrp::kPlanBicubic == LRP_BICUBIC, "interpolation numbering");
 
+// The geometry-cache key of a call: everything the coordinates depend on (lrp_geocache.h).
+lrp::GeoKey geo_key(const lrp_image *in, const lrp_image *out, const lrp::KParams &P, int num_samples, int device) {
+  lrp::GeoKey key;
+  std::memset(&key, 0, sizeof(key));
+  key.device = device;
+  key.out_type = out->lens.type;
+  key.in_mode = in_lens_mode(in->lens);
+  key.out_w = out->width, key.out_h = out->height, key.in_w = in->width, key.in_h = in->height;
+  key.has_rot = P.has_rot;
+  key.num_samples = num_samples;
+  key.out_lens = lrp::geo_canonical_lens(P.out_lens, out->lens.type), key.in_lens = lrp::geo_canonical_lens(P.in_lens, in->lens.type);
+  if (P.has_rot) std::memcpy(key.rot, P.rot, sizeof(key.rot));
+  return key;
+}
+
+// LRP_LANCZOS3 (include/lrp.h "Lanczos-3"; lrp_lanczos.hip): the planner is not asked — one kernel shape, one launch per frame
+// and per group of 8 channels (RGBA: one group of 4) on the caller's stream, like the pixel-kernel branch of enqueue_reproject.
+// num_samples == 1, whole images, "geo_cache" on: through the geometry cache under the key of every other sampler for this
+// geometry, as enqueue_packed does — the first launch writes the coordinate map as a side output, every later launch (of the
+// call, or of any sampler) loads it.  No allocation, no synchronisation and no lens table on this path.
+int enqueue_lanczos(const lrp_image *in, lrp_image *out, lrp::KParams P, const lrp_post *post, int device, hipStream_t stream, int n_batch, bool band) {
+  if (!lrp::launch_lanczos) return fail(LRP_ERR_HIP, "the Lanczos-3 kernels (lrp_lanczos.hip) are not part of this build");
+  const int ol = out->lens.type, im = in_lens_mode(in->lens);
+  lrp::GeoUse geo;
+  if (P.num_samples == 1 && !band && knob(kKnobGeoCache) != 0) {
+    lrp::geo_acquire(geo_key(in, out, P, P.num_samples, device), /*want_boxes=*/false, stream, &geo);
+    if (geo.mode == 1 || geo.mode == 2) {
+      P.geo_mode = geo.mode;
+      P.geo_xy = geo.xy;
+    }
+  }
+  const int n = n_batch > 0 ? n_batch : 1;
+  const int C = out->channels, group = C == 4 ? 4 : 8;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < n && e == hipSuccess; ++i)
+    for (int c0 = 0; c0 < C && e == hipSuccess; c0 += group) {
+      P.src = in[i].data + c0;
+      P.dst = out[i].data + c0;
+      P.ch_count = std::min(group, C - c0);
+      P.has_post = post != nullptr && c0 == 0; // post_process touches channels 0-2 only: all in the first group
+      e = lrp::launch_lanczos(P, ol, im, stream);
+      if (P.geo_mode == 1) P.geo_mode = 2; // the launch that writes the entry goes first; the rest follows on the same stream and reads it
+    }
+  lrp::geo_launched(&geo, stream, e == hipSuccess);
+  if (e != hipSuccess) return hip_fail(e, "Lanczos-3 kernel launch");
+  return LRP_OK;
+}
+
 // The launcher: asks the planner (lrp_plan.h — every decision is there, as pure functions the CPU tests call too), fetches what
 // the plan wants (output-lens tables, the column-separable x table, the geometry-cache entry) and enqueues the launches.
 int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int interpolation,
@@ -351,6 +406,7 @@ int enqueue_reproject(const lrp_image *in, lrp_image *out, int num_samples, int 
     P.y_offset = row_first;
     P.y_end = row_first + row_count;
   }
+  if (interpolation == LRP_LANCZOS3) return enqueue_lanczos(in, out, P, post, device, stream, n_batch, band);
   const int ol = out->lens.type, im = in_lens_mode(in->lens); // the cell of this call (lrp_cells.h)
   hipError_t e;
   lrp::TableLease lease; // pins the cached tables until every launch of this call is enqueued (scope end)
@@ -559,7 +615,7 @@ int validate_compose(const lrp_image *ins, int n_in, const lrp_image *out, int i
   if (mode != LRP_COMPOSE_FIRST && mode != LRP_COMPOSE_MEAN && mode != LRP_COMPOSE_FEATHER) return fail(LRP_ERR_BAD_ARG, "unknown compose mode");
   if (!ins || !out) return fail(LRP_ERR_NULL, "null image");
   for (int i = 0; i < n_in; ++i) { // (in->channels == out->channels is one of validate()'s checks)
-    const int st = validate(ins + i, out, interpolation, true);
+    const int st = validate(ins + i, out, interpolation, true, false);
     if (st != LRP_OK) return st;
   }
   const int first = in_lens_mode(ins[0].lens);
@@ -618,7 +674,7 @@ bool packed_addressable(const lrp_image &im, int format, int packed_channels) {
 
 // lrp_reproject_packed_device's checks, in the order include/lrp.h states.
 int validate_packed(const lrp_image *in, int in_format, int in_pch, const lrp_image *out, int out_format, int out_pch, int interpolation) {
-  const int st = validate(in, out, interpolation, true);
+  const int st = validate(in, out, interpolation, true, false);
   if (st != LRP_OK) return st;
   if (in_format == LRP_PIXEL_F32)
     return fail(LRP_ERR_BAD_ARG, "a float32 source needs no decode: call lrp_reproject_device + lrp_encode_pixels_device");
@@ -751,6 +807,11 @@ int lrp_lens_extensions(int mask) {
   return g_lens_ext.exchange(mask & (LRP_LENS_EXT_EQUISOLID | LRP_LENS_EXT_STEREOGRAPHIC), std::memory_order_relaxed);
 }
 
+int lrp_sampler_extensions(int mask) {
+  if (mask < 0) return g_sampler_ext.load(std::memory_order_relaxed);
+  return g_sampler_ext.exchange(mask & LRP_SAMPLER_EXT_LANCZOS3, std::memory_order_relaxed);
+}
+
 int lrp_debug_kernel(int choice) {
   if (choice < 0 || choice > 3) return kernel_choice();
   return g_knobs[kKnobKernel].exchange(choice, std::memory_order_relaxed);
@@ -812,7 +873,7 @@ const char *lrp_last_error(void) { return g_last_error.c_str(); }
 
 int lrp_reproject_device(const lrp_image *in, lrp_image *out, int num_samples, int interpolation,
                          const float *rotation, const lrp_post *post, int device, void *stream) {
-  int st = validate(in, out, interpolation, true);
+  int st = validate(in, out, interpolation, true, true);
   if (st != LRP_OK) return st;
   st = select_device(device);
   if (st != LRP_OK) return st;
@@ -821,7 +882,7 @@ int lrp_reproject_device(const lrp_image *in, lrp_image *out, int num_samples, i
 
 int lrp_reproject_rows_device(const lrp_image *in, lrp_image *out, int num_samples, int interpolation, const float *rotation,
                               const lrp_post *post, int row_first, int row_count, int device, void *stream) {
-  int st = validate(in, out, interpolation, true);
+  int st = validate(in, out, interpolation, true, true);
   if (st != LRP_OK) return st;
   if (row_first < 0 || row_count < 0 || row_first > out->height - row_count)
     return fail(LRP_ERR_BAD_ARG, "row band outside the output image");
@@ -898,7 +959,7 @@ int lrp_reproject_multi_device(const lrp_image *in, lrp_image *outs, int n_out, 
                                void *stream) {
   if (n_out < 0 || (n_out > 0 && !outs)) return fail(LRP_ERR_BAD_ARG, "bad output array");
   for (int i = 0; i < n_out; ++i) {
-    int st = validate(in, &outs[i], interpolation, true);
+    int st = validate(in, &outs[i], interpolation, true, true);
     if (st != LRP_OK) return st;
   }
   int st = select_device(device);
@@ -972,7 +1033,7 @@ int lrp_reproject_multi(const lrp_image *in, lrp_image *outs, int n_out, int num
   if (n_out < 0 || (n_out > 0 && !outs) || !devices || n_devices < 1 || n_devices > 64)
     return fail(LRP_ERR_BAD_ARG, "bad output array or device list");
   for (int i = 0; i < n_out; ++i) {
-    int st = validate(in, &outs[i], interpolation, true);
+    int st = validate(in, &outs[i], interpolation, true, true);
     if (st != LRP_OK) return st;
   }
   for (int d = 0; d < n_devices; ++d) {
@@ -1114,7 +1175,7 @@ int lrp_reproject_batch_device(const lrp_image *ins, lrp_image *outs, int n, int
   if (n < 0 || (n > 0 && (!ins || !outs))) return fail(LRP_ERR_BAD_ARG, "bad image arrays");
   if (n == 0) return LRP_OK;
   for (int i = 0; i < n; ++i) {
-    int st = validate(&ins[i], &outs[i], interpolation, true);
+    int st = validate(&ins[i], &outs[i], interpolation, true, true);
     if (st != LRP_OK) return st;
     const bool same = ins[i].width == ins[0].width && ins[i].height == ins[0].height && ins[i].channels == ins[0].channels &&
                       outs[i].width == outs[0].width && outs[i].height == outs[0].height &&
@@ -1253,7 +1314,7 @@ int lrp_context_submit_packed(lrp_context *ctx, const lrp_image *in, int in_form
                               int interpolation, const float *rotation, const lrp_post *post, int *ticket) {
   if (!ctx) return fail(LRP_ERR_NULL, "null context");
   if (ticket) *ticket = -1;
-  int st = validate(in, out, interpolation, true);
+  int st = validate(in, out, interpolation, true, true);
   if (st != LRP_OK) return st;
   if (!format_ok(in_format) || !format_ok(out_format) || in_packed_channels < 1 || out_packed_channels < 1 ||
       in_packed_channels > 64 || out_packed_channels > 64)
@@ -1349,7 +1410,7 @@ void return_context(lrp_context *c) {
 
 int lrp_reproject(const lrp_image *in, lrp_image *out, int num_samples, int interpolation, const float *rotation,
                   const lrp_post *post, int device) {
-  int st = validate(in, out, interpolation, true);
+  int st = validate(in, out, interpolation, true, true);
   if (st != LRP_OK) return st;
   lrp_context *c = nullptr;
   st = borrow_context(device, &c);

@@ -81,6 +81,10 @@ typedef enum lrp_lens_type {
 
 /* reference src/reproject.hpp:16-20 (enum Interpolation) */
 typedef enum lrp_interpolation { LRP_NEAREST = 0, LRP_BILINEAR = 1, LRP_BICUBIC = 2 } lrp_interpolation;
+/* Lanczos-3: an interpolation value outside the reference's enum (which keeps its three members), accepted only while
+ * lrp_sampler_extensions(LRP_SAMPLER_EXT_LANCZOS3) is set; see "Lanczos-3" below. */
+#define LRP_LANCZOS3 3
+#define LRP_SAMPLER_EXT_LANCZOS3 1
 
 /* reference src/reproject.hpp:7 (enum DataLayout); carried, never read by the kernels */
 typedef enum lrp_data_layout { LRP_RGB = 0, LRP_RGBA = 1, LRP_RGBZ = 2, LRP_RGBAZ = 3 } lrp_data_layout;
@@ -143,6 +147,11 @@ int lrp_abi_version(void);
  * and returns the previous one; a negative value only queries.  The known bits (LRP_LENS_EXT_EQUISOLID,
  * LRP_LENS_EXT_STEREOGRAPHIC) are kept, the rest dropped.  With both on, every value of lrp_lens_type renders. */
 int lrp_lens_extensions(int mask);
+/* Process-wide mask of opt-in sampler extensions (LRP_SAMPLER_EXT_*), 0 by default: every entry point then rejects
+ * interpolation 3 as the reference does, with LRP_ERR_INTERPOLATION.  The semantics of lrp_lens_extensions: sets the mask for
+ * subsequent calls of all threads (each call reads it once) and returns the previous one; a negative value only queries; the
+ * known bit (LRP_SAMPLER_EXT_LANCZOS3) is kept, the rest dropped. */
+int lrp_sampler_extensions(int mask);
 /* Number of usable HIP devices (0 when there is none; never negative). */
 int lrp_device_count(void);
 /* Static text for a status code. */
@@ -448,6 +457,50 @@ int lrp_context_wait_ticket(lrp_context *ctx, int ticket);
 int lrp_reproject_packed_device(const lrp_image *in, int in_format, int in_packed_channels, lrp_image *out, int out_format,
                                 int out_packed_channels, unsigned out_fill, int num_samples, int interpolation,
                                 const float *rotation, const lrp_post *post, int device, void *stream);
+
+/* ---- Lanczos-3 ---------------------------------------------------------------------------- */
+
+/* LRP_LANCZOS3 (interpolation 3, with LRP_SAMPLER_EXT_LANCZOS3 on): a fourth sampler with a 6 x 6 footprint, the filter that
+ * ffmpeg v360, Hugin, OpenCV and Pillow offer under this name.  The reference has none, so this text is the definition.
+ *
+ * Accepted by every entry point that renders through lrp_reproject_device's launcher: lrp_reproject, lrp_reproject_device,
+ * lrp_reproject_rows_device, lrp_reproject_batch_device, lrp_reproject_multi_device, lrp_reproject_multi,
+ * lrp_context_submit, lrp_context_submit_packed.  With the bit off they return LRP_ERR_INTERPOLATION where the reference's
+ * interpolation check stands in the validation order.  lrp_compose_device and lrp_reproject_packed_device reject
+ * interpolation 3 at that position whether the bit is on or off.
+ *
+ * All arithmetic is binary32, un-fused, in the order written.  sinf_ and cosf_ are the glibc clones of lrp_math.h (the same
+ * bits on host and device).  trunc_x86 (int(float) as cvttss2si: NaN, infinities and out-of-range give INT_MIN),
+ * column<Loop> (wrapping sources wrap, others clamp), clamp_index and unit_clamp (std::max(0.0f, std::min(1.0f, v)) in
+ * libstdc++'s comparison direction: NaN -> 1) are those of the bicubic sampler.  kPi = 0x1.921fb6p+1f,
+ * kSin60 = 0x1.bb67aep-1f.  (sx, sy) are the top-left-origin source coordinates every sampler receives.
+ *
+ * Taps, k = -2 .. 3:   ix_k = column<Loop>(trunc_x86(sx + (float)k), in_w)   (k = 0: trunc_x86(sx))
+ *                      iy_k = clamp_index(trunc_x86(sy + (float)k), in_h - 1)
+ *                      fx = unit_clamp(sx - (float)ix_0),  fy = unit_clamp(sy - (float)iy_0)
+ * — the fractions come from the clamped index, as in the reference's bicubic.
+ *
+ * Half weights  half(t) -> h0, h1, h2  for the distances t, t + 1, t + 2:
+ *   p = kPi * t;  s = sinf_(p);  q = p / 3.0f;  s3 = sinf_(q);  c3 = cosf_(q)
+ *   h0 = (p == 0.0f) ? 1.0f : (3.0f * (s / p)) * (s3 / p)
+ *   p1 = kPi * (t + 1.0f);  a1 = (0.5f * s3) + (kSin60 * c3);  h1 = (3.0f * ((-s) * a1)) / (p1 * p1)
+ *   p2 = kPi * (t + 2.0f);  a2 = (kSin60 * c3) - (0.5f * s3);  h2 = (3.0f * (s * a2)) / (p2 * p2)
+ * i.e. sinc(d) sinc(d / 3) with sin(pi (t + j)) = +-sin(pi t) and sin(pi (t + j) / 3) from the angle sum: two
+ * trigonometric calls per half instead of six.
+ *
+ * Axis weights from f:  f == 0.0f: {0, 0, 1, 0, 0, 0};  f == 1.0f: {0, 0, 0, 1, 0, 0}  (+0.0f and 1.0f);  otherwise
+ *   L = half(f), R = half(1.0f - f);  r = {L2, L1, L0, R0, R1, R2}  (tap order k = -2 .. 3)
+ *   W = ((((r0 + r1) + r2) + r3) + r4) + r5;  w_k = r_k / W
+ * The right-hand taps use 1 - f, so the weight next to the nearest tap stays accurate on both sides.
+ *
+ * Blend, vertical per tap column and then horizontal, like bicubicInterpolate; p(i, j) is the texel at (ix_i, iy_j):
+ *   per tap column i and channel:  col_i = wy_0 * p(i, 0);  col_i = col_i + wy_j * p(i, j)  for j = 1 .. 5
+ *   out = wx_0 * col_0;  out = out + wx_i * col_i  for i = 1 .. 5          (each step a multiply, then an add)
+ * Sub-samples (acc = 0; acc += out, ssx outer, ssy inner), normalize, the fused post and the channel rules are those of
+ * every other sampler.
+ *
+ * A num_samples == 1 call of a whole image goes through the geometry cache under the key of the other samplers: entries are
+ * shared with them in both directions. */
 
 /* ---- synthetic frames (bench / tests) -------------------------------------- */
 
