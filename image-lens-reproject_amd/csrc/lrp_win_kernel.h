@@ -51,6 +51,15 @@ __device__ unsigned g_tier_stats[8]; // coefficient, raw, direct, corner, beyond
 constexpr int frame_loop_hoist(int in_mode, int ch) {
   return (ch == 5 || (in_mode == kInRect && ch == 3)) ? 1 : 2;
 }
+// Which of those kernels map lanes to pixels by LDS service group (lrp_win_plan.h win_lane_pixel<true>) instead of row-major.
+// The grouped map removes 40 % of the bank-conflict cycles of the coefficient tier's reads wherever it runs, but the time
+// follows only where the LDS array is the busiest unit: the RGBA kernel of the equidistant source (the headline: -1.0 % per
+// frame in bench.py, -1.3 % in kbench; fisheye -> fisheye level).  Everywhere else — 16-frame launches, us per frame,
+// profiles/r10_lds_account.txt — it is level or loses: equidistant RGB -0.5 % / +0.4 %, RGBAZ +0.9 % / +0.4 %, the panorama
+// sources +0.8 .. +1.3 % on four of five RGBA rows and +0.7 .. +1.6 % RGBAZ, the rectilinear source level.  They keep row-major.
+constexpr bool frame_loop_grouped_lanes(int in_mode, int ch) {
+  return in_mode == kInEquidistant && ch == 4;
+}
 // an LDS byte address (a multiple of the size of T) as a pointer; the reads through it are ds_read: the address space is inferred from the cast
 template <class T> __device__ __forceinline__ const T *lds_ptr(uint32_t byte_addr) {
   return static_cast<const T *>(__builtin_assume_aligned((const T *)(__attribute__((address_space(3))) const T *)(uintptr_t)byte_addr, sizeof(T)));
@@ -342,7 +351,7 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
   auto image_of = [&](int g) { return ((QMode == 2 ? 2 * g : g) ^ g_flip) & (QMode == 2 ? kAllMirrors : -1); };
   // workgroup tile = 16 kWinWaves x 16G (x 16 of the quadrant when mirrored): one strip per wavefront
   int prow, pcol; // this lane's pixel of a pass
-  win_lane_pixel(lane, prow, pcol);
+  win_lane_pixel<kOneBlock && frame_loop_grouped_lanes(InMode, CH)>(lane, prow, pcol);
   // SS: this lane's pixel of the pass (pcol; every lane of a pass lies in one output row) and its sub-sample; wave-uniform:
   // sub-samples per pixel and pixels per pass.  (The divisors are 4, 9, 16 and 2, 3, 4: a multiply and a shift.)
   const int ss_ns = SS ? Pk.num_samples : 1, ss_n = ss_ns * ss_ns, ss_npx = SS ? 64 / ss_n : kBlkW;
