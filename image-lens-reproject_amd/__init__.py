@@ -663,6 +663,67 @@ def reproject_packed(in_image, in_format, in_data, out_image, out_format, out_da
     _check(st)
 
 
+def compose_packed(in_images, in_format, in_datas, out_image, out_format, out_data, out_fill, interpolation, rotation_matrices=None,
+                   mode=ComposeMode.FIRST, post=None, count=None, device=None, stream=None):
+    """lrp_compose_packed_device (include/lrp.h "compose, packed pixels"): compose() on sources and an output in their file
+    formats, as one launch — the bytes of decode_pixels per source -> compose -> encode_pixels without the float32 staging
+    images.  `in_datas` (one per source, all in `in_format` and of one packed channel count) and `out_data` are contiguous CUDA
+    tensors of shape (height, width, packed_channels) as reproject_packed() takes them; the images describe the float geometry
+    (their own data is not looked at).  rotation_matrices, mode, post and count (None, True or a tensor to fill; returned) as in
+    compose().  Asynchronous on `stream` (default: torch's current stream)."""
+    lib = _native.load()
+    n = len(in_images)
+    in_datas = list(in_datas)
+    if len(in_datas) != n:
+        raise ValueError(f"compose_packed(): {n} source images but {len(in_datas)} packed tensors")
+    named = [(f"in_datas[{i}]", t, int(in_format), im) for i, (t, im) in enumerate(zip(in_datas, in_images))]
+    named.append(("out_data", out_data, int(out_format), out_image))
+    # reproject_packed()'s checks, for every tensor
+    sample_bytes = {int(PixelFormat.F32): 4, int(PixelFormat.F16): 2, int(PixelFormat.U8_GAMMA): 1}
+    for name, t, fmt, im in named:
+        if not _is_torch(t) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"compose_packed() takes device tensors only: {name} must be a contiguous CUDA tensor")
+        if fmt in sample_bytes and t.element_size() != sample_bytes[fmt]:
+            raise ValueError(f"{name}: elements of {t.element_size()} bytes ({t.dtype}) for a format of {sample_bytes[fmt]}-byte samples")
+        if t.dim() < 1 or t.numel() != im.width * im.height * t.shape[-1]:
+            raise ValueError(f"{name}: packed tensors must hold height*width pixels of shape[-1] samples")
+    if any(t.shape[-1] != in_datas[0].shape[-1] for t in in_datas[1:]):
+        raise ValueError("compose_packed(): every source must have the same number of packed channels")
+    want_count = count is not None and count is not False
+    if want_count and count is not True:
+        import torch
+
+        if (not _is_torch(count) or count.dtype != torch.uint8 or not count.is_cuda or not count.is_contiguous()
+                or count.numel() != out_image.height * out_image.width):
+            raise ValueError("count must be a contiguous uint8 CUDA tensor with height*width elements")
+    if device is None:
+        device = out_data.device.index
+    plane = None
+    if want_count:
+        import torch
+
+        plane = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}") if count is True else count
+    arr = (LrpImage * max(n, 1))()
+    cout = LrpImage()
+    for c, im, t in [(arr[i], im, t) for i, (im, t) in enumerate(zip(in_images, in_datas))] + [(cout, out_image, out_data)]:
+        c.lens = im.lens.to_c()
+        c.width, c.height, c.channels = im.width, im.height, im.channels
+        c.data = t.data_ptr()
+        c.data_layout = im.data_layout
+    rot, keep = None, None
+    if rotation_matrices is not None:
+        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
+        rot = keep.ctypes.data
+    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    st = lib.lrp_compose_packed_device(arr, n, int(in_format), int(in_datas[0].shape[-1]) if n else 0, rot, ctypes.byref(cout), int(out_format),
+                                       int(out_data.shape[-1]), int(out_fill), int(interpolation), int(mode),
+                                       ctypes.byref(cpost) if cpost is not None else None, plane.data_ptr() if plane is not None else None,
+                                       device, _stream_handle(stream))
+    del keep
+    _check(st)
+    return plane
+
+
 def pixel_tables():
     """(decode[256], threshold[256]) of LRP_PIXEL_U8_GAMMA as the host's powf made them."""
     dec = (ctypes.c_float * 256)()

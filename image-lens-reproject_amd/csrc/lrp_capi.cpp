@@ -22,6 +22,7 @@
 
 #include "../../include/lrp.h"
 #include "lrp_compose.h"
+#include "lrp_compose_packed.h"
 #include "lrp_geocache.h"
 #include "lrp_packed.h"
 #include "lrp_params.h"
@@ -48,6 +49,8 @@ __attribute__((weak)) hipError_t launch_coverage(KParams P, int out_lens, int in
 __attribute__((weak)) hipError_t launch_compose(const ComposeParams &P, int out_lens, int in_mode, int interpolation, hipStream_t stream);
 // lrp_packed.hip, weak like launch_coverage (enqueue_packed).
 __attribute__((weak)) hipError_t launch_packed(PackedParams P, int in_format, int out_lens, int in_mode, int interpolation, int device, hipStream_t stream);
+// lrp_compose_packed.hip, weak like launch_coverage (enqueue_compose_packed).
+__attribute__((weak)) hipError_t launch_compose_packed(ComposePackedParams P, int in_format, int out_lens, int in_mode, int interpolation, int device, hipStream_t stream);
 // lrp_lanczos.hip, weak like launch_coverage (enqueue_lanczos).
 __attribute__((weak)) hipError_t launch_lanczos(KParams P, int out_lens, int in_mode, hipStream_t stream);
 hipError_t launch_post_process(float *data, uint32_t n_pixels, int channels, float exposure, float reinhard,
@@ -733,6 +736,59 @@ int enqueue_packed(const lrp_image *in, int in_format, int in_pch, lrp_image *ou
   return LRP_OK;
 }
 
+// lrp_compose_packed_device's checks, in the order include/lrp.h states: those of lrp_compose_device, then those
+// lrp_reproject_packed_device adds to lrp_reproject_device's.
+int validate_compose_packed(const lrp_image *ins, int n_in, int in_format, int in_pch, const lrp_image *out, int out_format, int out_pch,
+                            int interpolation, int mode) {
+  const int st = validate_compose(ins, n_in, out, interpolation, mode);
+  if (st != LRP_OK) return st;
+  if (in_format == LRP_PIXEL_F32)
+    return fail(LRP_ERR_BAD_ARG, "float32 sources need no decode: call lrp_compose_device + lrp_encode_pixels_device");
+  if (!format_ok(in_format) || !format_ok(out_format)) return fail(LRP_ERR_BAD_ARG, "unknown pixel format");
+  if (in_pch < 1 || out_pch < 1) return fail(LRP_ERR_BAD_ARG, "packed channel counts must be >= 1");
+  if (out->channels > lrp::kPackedMaxChannels)
+    return fail(LRP_ERR_CHANNELS, "lrp_compose_packed_device composes at most " + std::to_string(lrp::kPackedMaxChannels) + " channels");
+  bool fits = packed_addressable(*out, out_format, out_pch);
+  for (int i = 0; i < n_in; ++i) fits = fits && packed_addressable(ins[i], in_format, in_pch);
+  if (!fits) return fail(LRP_ERR_BAD_DIMS, "a packed image of more than 2^31 bytes cannot be addressed (the packed compose kernel forms 32-bit byte offsets)");
+  return LRP_OK;
+}
+
+// One launch of the packed compose kernel (lrp_compose_packed.hip); no table but the two 8-bit ones, no geometry-cache entry, no
+// allocation.
+int enqueue_compose_packed(const lrp_image *ins, int n_in, int in_format, int in_pch, const float *rotations, const lrp_image *out,
+                           int out_format, int out_pch, unsigned out_fill, int interpolation, int mode, const lrp_post *post, uint8_t *count,
+                           int device, hipStream_t stream) {
+  if (!lrp::launch_compose_packed) return fail(LRP_ERR_HIP, "the packed compose kernels (lrp_compose_packed.hip) are not part of this build");
+  lrp::ComposePackedParams C;
+  std::memset(&C, 0, sizeof(C));
+  for (int i = 0; i < n_in; ++i) { // the per-source values as make_params() packs them for a reprojection of source i
+    const lrp::KParams P = make_params(ins + i, out, 1, rotations ? rotations + 9 * i : nullptr, post);
+    if (i == 0) {
+      C.out_w = P.out_w, C.out_h = P.out_h, C.channels = P.channels;
+      C.out_lens = P.out_lens;
+      C.has_post = P.has_post;
+      C.exposure = P.exposure, C.reinhard = P.reinhard;
+    }
+    lrp::ComposePackedSource &S = C.src[i];
+    S.data = ins[i].data;
+    S.in_w = P.in_w, S.in_h = P.in_h;
+    S.lens = P.in_lens;
+    S.has_rot = P.has_rot;
+    std::memcpy(S.rot, P.rot, sizeof(S.rot));
+  }
+  C.dst = out->data;
+  C.count = count;
+  C.in_channels = in_pch, C.out_channels = out_pch;
+  C.out_format = out_format;
+  C.out_fill = out_fill;
+  C.n_src = n_in;
+  C.mode = mode;
+  const hipError_t e = lrp::launch_compose_packed(C, in_format, out->lens.type, in_lens_mode(ins[0].lens), interpolation, device, stream);
+  if (e != hipSuccess) return hip_fail(e, "packed compose kernel launch");
+  return LRP_OK;
+}
+
 // Grow-only device / pinned buffer.
 struct Buffer {
   void *ptr = nullptr;
@@ -919,6 +975,17 @@ int lrp_reproject_packed_device(const lrp_image *in, int in_format, int in_packe
   if (st != LRP_OK) return st;
   return enqueue_packed(in, in_format, in_packed_channels, out, out_format, out_packed_channels, out_fill, num_samples, interpolation,
                         rotation, post, device, (hipStream_t)stream);
+}
+
+int lrp_compose_packed_device(const lrp_image *ins, int n_in, int in_format, int in_packed_channels, const float *rotations,
+                              const lrp_image *out, int out_format, int out_packed_channels, unsigned out_fill, int interpolation, int mode,
+                              const lrp_post *post, uint8_t *count, int device, void *stream) {
+  int st = validate_compose_packed(ins, n_in, in_format, in_packed_channels, out, out_format, out_packed_channels, interpolation, mode);
+  if (st != LRP_OK) return st;
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_compose_packed(ins, n_in, in_format, in_packed_channels, rotations, out, out_format, out_packed_channels, out_fill,
+                                interpolation, mode, post, count, device, (hipStream_t)stream);
 }
 
 namespace {

@@ -72,7 +72,9 @@ template <int Fmt, bool Vec> struct PackedTaps {
 
 // One output pixel in out_format: the first out_copy samples encoded as encode_kernel does, out_fill behind them.  Four
 // samples at an aligned base leave as one store; anything else as one store per sample.  Non-temporal, like store_texel.
-template <int CH> __device__ __forceinline__ void store_packed(const PackedParams &P, const float *thr, uint32_t px, const Texel<CH> &t) {
+// Out: the kernarg block of the calling kernel — PackedParams, or ComposePackedParams (lrp_compose_packed.h) — of which the
+// output fields dst, out_pitch, out_copy, out_channels, out_format, out_fill and out_vec are read.
+template <int CH, class Out> __device__ __forceinline__ void store_packed(const Out &P, const float *thr, uint32_t px, const Texel<CH> &t) {
   constexpr int L = texel_lanes<CH>();
   uint8_t *const o = static_cast<uint8_t *>(P.dst) + px * (uint32_t)P.out_pitch;
   const int copy = P.out_copy, n = P.out_channels;

@@ -458,6 +458,46 @@ int lrp_reproject_packed_device(const lrp_image *in, int in_format, int in_packe
                                 int out_packed_channels, unsigned out_fill, int num_samples, int interpolation,
                                 const float *rotation, const lrp_post *post, int device, void *stream);
 
+/* ---- compose, packed pixels: 8-bit and half sources composed into a packed output by one launch -------- */
+
+/* lrp_compose_device on sources and an output in their real formats: the frames of a camera rig — RGBA8 from a video decoder,
+ * binary16 from an EXR reader —, several of them, stitched into one 8-bit, binary16 or float output by ONE launch.  No float32
+ * staging image exists: a source's taps are decoded as they are loaded and the composed value is encoded as it is stored.
+ * ins[i].data / out->data are device pointers to packed samples of any alignment (each source's own), with the meaning
+ * lrp_reproject_packed_device gives them: ins[i].width x ins[i].height texels of in_packed_channels samples in in_format — one
+ * format and one packed channel count for all sources —, out->width x out->height pixels of out_packed_channels samples in
+ * out_format.  C = ins[i].channels = out->channels (at most 8) is the channel count of the float images the kernels of the
+ * chain would see.  Sizes, lens parameters and rotations differ per source, as in lrp_compose_device.
+ *
+ * Definition.  The bytes written to out->data and to count are exactly those of this chain with float32 temporaries tmp_i (one
+ * per source) and tmp_out, each of C channels:
+ *   for each i:  lrp_decode_pixels_device(ins[i].data, in_format, in_packed_channels, tmp_i, C, ...)
+ *   lrp_compose_device(tmp_0 .. tmp_{n_in - 1} -> tmp_out, rotations, interpolation, mode, post, count)
+ *   lrp_encode_pixels_device(tmp_out, C, out->data, out_format, out_packed_channels, out_fill, ...)
+ * the corner cases of both parents included: the channels of a source beyond in_packed_channels are +0.0f taps that go through
+ * the sampler's arithmetic; packed source samples beyond C are not read; output samples beyond C are out_fill (the low 8 / 16
+ * bits; for LRP_PIXEL_F32 the fill's bit pattern), also for a pixel no source covers; such a k == 0 pixel is +0.0f in the first
+ * C channels before the encode, whatever post is (code 0 for 8-bit); the 8-bit encode clamps as lrp_encode_pixels_device does —
+ * NaN becomes 255, -0 becomes 0.  Nothing new is defined about arithmetic.  Where a sample of the chain is a NaN (a NaN or an
+ * infinity among the taps of a half source, or inf - inf in a blend), its sign and payload are the chain's; an 8-bit source
+ * cannot produce a NaN, an 8-bit output has none.
+ *
+ * in_format is LRP_PIXEL_F16 or LRP_PIXEL_U8_GAMMA (float32 sources need no decode: lrp_compose_device +
+ * lrp_encode_pixels_device); out_format is any of the three.
+ *
+ * Asynchronous on `stream`; allocates nothing, builds no lens table, neither reads nor writes the geometry cache (the
+ * lrp_geometry_cache_stats counters do not move).  The first call on a device uploads the two 8-bit tables (2 KiB, one
+ * synchronisation, like the conversion kernels and lrp_reproject_packed_device, whose copy it shares).
+ * Errors, all before a device is touched, in this order: the errors of lrp_compose_device in its order and with its statuses
+ * and texts (n_in / mode; NULL; per source the checks of lrp_reproject_device(ins + i, out) with interpolation 0 .. 2 only; the
+ * mix of source modes); LRP_ERR_BAD_ARG for in_format == LRP_PIXEL_F32, an unknown format or a packed channel count < 1;
+ * LRP_ERR_CHANNELS for C > 8; LRP_ERR_BAD_DIMS for a packed image — a source or the output: width x height x packed channels x
+ * bytes per sample — of more than 2^31 bytes (the kernel forms 32-bit byte offsets). */
+int lrp_compose_packed_device(const lrp_image *ins, int n_in, int in_format, int in_packed_channels,
+                              const float *rotations /* n_in x 9, or NULL */, const lrp_image *out, int out_format,
+                              int out_packed_channels, unsigned out_fill, int interpolation, int mode, const lrp_post *post,
+                              uint8_t *count /* out->width * out->height bytes, or NULL */, int device, void *stream);
+
 /* ---- Lanczos-3 ---------------------------------------------------------------------------- */
 
 /* LRP_LANCZOS3 (interpolation 3, with LRP_SAMPLER_EXT_LANCZOS3 on): a fourth sampler with a 6 x 6 footprint, the filter that
@@ -466,8 +506,8 @@ int lrp_reproject_packed_device(const lrp_image *in, int in_format, int in_packe
  * Accepted by every entry point that renders through lrp_reproject_device's launcher: lrp_reproject, lrp_reproject_device,
  * lrp_reproject_rows_device, lrp_reproject_batch_device, lrp_reproject_multi_device, lrp_reproject_multi,
  * lrp_context_submit, lrp_context_submit_packed.  With the bit off they return LRP_ERR_INTERPOLATION where the reference's
- * interpolation check stands in the validation order.  lrp_compose_device and lrp_reproject_packed_device reject
- * interpolation 3 at that position whether the bit is on or off.
+ * interpolation check stands in the validation order.  lrp_compose_device, lrp_compose_packed_device and
+ * lrp_reproject_packed_device reject interpolation 3 at that position whether the bit is on or off.
  *
  * All arithmetic is binary32, un-fused, in the order written.  sinf_ and cosf_ are the glibc clones of lrp_math.h (the same
  * bits on host and device).  trunc_x86 (int(float) as cvttss2si: NaN, infinities and out-of-range give INT_MIN),
