@@ -15,7 +15,9 @@ the HIP library and a GPU every compute call raises.  Beyond the reference:
 coverage(in_image, out_image, num_samples, rotation_matrix) tells which output
 pixels the source image can see (device tensors), and
 compose(in_images, out_image, interpolation, rotation_matrices, mode) renders
-several source images into one output (device tensors).
+several source images into one output (device tensors), and
+compose_ss(in_images, out_image, num_samples, interpolation, ...) does so with
+num_samples^2 sub-samples per pixel (anti-aliased stitching).
 
 The directory name contains a hyphen (it is the name the build contract fixes);
 import it with importlib.import_module("image-lens-reproject_amd").
@@ -370,6 +372,53 @@ def compose(in_images, out_image, interpolation, rotation_matrices=None, mode=Co
     del keep
     _check(st)
     return plane
+
+
+def compose_ss(in_images, out_image, num_samples, interpolation, rotation_matrices=None, mode=ComposeMode.FIRST, post=None, count=None,
+               coverage=None, device=None, stream=None):
+    """lrp_compose_ss_device (include/lrp.h "compose, supersampled"): compose() with num_samples x num_samples sub-samples per
+    output pixel, by one launch — which sources cover a point is decided per sub-sample, every covered sub-sample is composed
+    under `mode`, and the pixel is the mean of its covered sub-samples (+0.0 where none is).  Device tensors only; asynchronous
+    on `stream`.  count / coverage: None, True (a new (height, width) uint8 CUDA tensor) or such a tensor to fill — count the
+    number of sources that cover at least one sub-sample of the pixel, coverage the number of covered sub-samples, 0 ..
+    num_samples^2.  Returns (count plane or None, coverage plane or None)."""
+    lib = _native.load()
+    n = len(in_images)
+    wanted = {}
+    for name, arg in (("count", count), ("coverage", coverage)):
+        wanted[name] = arg is not None and arg is not False
+        if wanted[name] and arg is not True:
+            import torch
+
+            if (not _is_torch(arg) or arg.dtype != torch.uint8 or not arg.is_cuda or not arg.is_contiguous()
+                    or arg.numel() != out_image.height * out_image.width):
+                raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor with height*width elements")
+    if not out_image.on_device() or not all(i.on_device() for i in in_images):
+        raise ValueError("compose_ss() takes device tensors only: the data of every input image and of the output must be a CUDA tensor")
+    if device is None:
+        device = out_image.data.device.index
+    planes = {}
+    for name, arg in (("count", count), ("coverage", coverage)):
+        planes[name] = None
+        if wanted[name]:
+            import torch
+
+            planes[name] = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}") if arg is True else arg
+    arr = (LrpImage * max(n, 1))(*[i.to_c() for i in in_images])
+    cout = out_image.to_c()
+    rot, keep = None, None
+    if rotation_matrices is not None:
+        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
+        rot = keep.ctypes.data
+    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    st = lib.lrp_compose_ss_device(arr, n, rot, ctypes.byref(cout), int(num_samples), int(interpolation), int(mode),
+                                   ctypes.byref(cpost) if cpost is not None else None,
+                                   planes["count"].data_ptr() if planes["count"] is not None else None,
+                                   planes["coverage"].data_ptr() if planes["coverage"] is not None else None,
+                                   device, _stream_handle(stream))
+    del keep
+    _check(st)
+    return planes["count"], planes["coverage"]
 
 
 def reproject_multi(in_image, out_images, num_samples, interpolation, rotation_matrices=None, post=None, device=None,

@@ -102,6 +102,11 @@ SYMBOLS = {
         [_P(LrpImage), ctypes.c_int, _FLOATP, _P(LrpImage), ctypes.c_int, ctypes.c_int, _P(LrpPost), ctypes.c_void_p, ctypes.c_int,
          ctypes.c_void_p],
     ),
+    "lrp_compose_ss_device": (
+        ctypes.c_int,
+        [_P(LrpImage), ctypes.c_int, _FLOATP, _P(LrpImage), ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(LrpPost), ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
+    ),
     "lrp_reproject_multi": (
         ctypes.c_int,
         [_P(LrpImage), _P(LrpImage), ctypes.c_int, ctypes.c_int, ctypes.c_int, _FLOATP, _P(LrpPost), _P(ctypes.c_int), ctypes.c_int],

@@ -23,6 +23,7 @@
 #include "../../include/lrp.h"
 #include "lrp_compose.h"
 #include "lrp_compose_packed.h"
+#include "lrp_compose_ss.h"
 #include "lrp_geocache.h"
 #include "lrp_packed.h"
 #include "lrp_params.h"
@@ -47,6 +48,8 @@ hipError_t launch_corner_fill(const KParams &P, hipStream_t stream);
 __attribute__((weak)) hipError_t launch_coverage(KParams P, int out_lens, int in_mode, uint8_t *plane, int mask_image, int alpha_channel, hipStream_t stream);
 // lrp_compose.hip, weak like launch_coverage (enqueue_compose).
 __attribute__((weak)) hipError_t launch_compose(const ComposeParams &P, int out_lens, int in_mode, int interpolation, hipStream_t stream);
+// lrp_compose_ss.hip, weak like launch_compose (enqueue_compose_ss).
+__attribute__((weak)) hipError_t launch_compose_ss(const ComposeSsParams &P, int out_lens, int in_mode, int interpolation, hipStream_t stream);
 // lrp_packed.hip, weak like launch_coverage (enqueue_packed).
 __attribute__((weak)) hipError_t launch_packed(PackedParams P, int in_format, int out_lens, int in_mode, int interpolation, int device, hipStream_t stream);
 // lrp_compose_packed.hip, weak like launch_coverage (enqueue_compose_packed).
@@ -663,6 +666,43 @@ int enqueue_compose(const lrp_image *ins, int n_in, const float *rotations, cons
   return LRP_OK;
 }
 
+// One launch of the supersampled compose kernel per group of 8 channels (lrp_compose_ss.hip), each of which writes the planes;
+// no table, no geometry-cache entry, no allocation.
+int enqueue_compose_ss(const lrp_image *ins, int n_in, const float *rotations, const lrp_image *out, int num_samples, int interpolation,
+                       int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, hipStream_t stream) {
+  if (!lrp::launch_compose_ss) return fail(LRP_ERR_HIP, "the supersampled compose kernels (lrp_compose_ss.hip) are not part of this build");
+  lrp::ComposeSsParams C;
+  std::memset(&C, 0, sizeof(C));
+  for (int i = 0; i < n_in; ++i) { // the per-source values as make_params() packs them for a reprojection of source i
+    const lrp::KParams P = make_params(ins + i, out, num_samples, rotations ? rotations + 9 * i : nullptr, post);
+    if (i == 0) {
+      C.out_w = P.out_w, C.out_h = P.out_h, C.channels = P.channels;
+      C.out_lens = P.out_lens;
+      C.exposure = P.exposure, C.reinhard = P.reinhard;
+    }
+    lrp::ComposeSource &S = C.src[i];
+    S.in_w = P.in_w, S.in_h = P.in_h;
+    S.lens = P.in_lens;
+    S.has_rot = P.has_rot;
+    std::memcpy(S.rot, P.rot, sizeof(S.rot));
+  }
+  C.n_src = n_in;
+  C.mode = mode;
+  C.num_samples = num_samples;
+  C.count = count;
+  C.coverage = coverage;
+  const int channels = out->channels, group = lrp::kComposeMaxChannels;
+  for (int c0 = 0; c0 < channels; c0 += group) {
+    for (int i = 0; i < n_in; ++i) C.src[i].data = ins[i].data + c0;
+    C.dst = out->data + c0;
+    C.ch_count = std::min(group, channels - c0);
+    C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
+    const hipError_t e = lrp::launch_compose_ss(C, out->lens.type, in_lens_mode(ins[0].lens), interpolation, stream);
+    if (e != hipSuccess) return hip_fail(e, "supersampled compose kernel launch");
+  }
+  return LRP_OK;
+}
+
 static_assert((int)lrp::kPackedF32 == LRP_PIXEL_F32 && (int)lrp::kPackedF16 == LRP_PIXEL_F16 && (int)lrp::kPackedU8 == LRP_PIXEL_U8_GAMMA, "lrp_packed.h numbers pixel formats like include/lrp.h");
 
 bool format_ok(int f) { return f == LRP_PIXEL_F32 || f == LRP_PIXEL_F16 || f == LRP_PIXEL_U8_GAMMA; }
@@ -964,6 +1004,17 @@ int lrp_compose_device(const lrp_image *ins, int n_in, const float *rotations, c
   st = select_device(device);
   if (st != LRP_OK) return st;
   return enqueue_compose(ins, n_in, rotations, out, interpolation, mode, post, count, (hipStream_t)stream);
+}
+
+int lrp_compose_ss_device(const lrp_image *ins, int n_in, const float *rotations, const lrp_image *out, int num_samples, int interpolation,
+                          int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, int device, void *stream) {
+  int st = validate_compose(ins, n_in, out, interpolation, mode);
+  if (st != LRP_OK) return st;
+  if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
+    return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_compose_ss(ins, n_in, rotations, out, num_samples, interpolation, mode, post, count, coverage, (hipStream_t)stream);
 }
 
 int lrp_reproject_packed_device(const lrp_image *in, int in_format, int in_packed_channels, lrp_image *out, int out_format,

@@ -300,7 +300,7 @@ int lrp_coverage_device(const lrp_image *in, const lrp_image *out, int num_sampl
  * output by one kernel launch (per group of 8 channels).  Per output pixel the target ray is computed once, each source is
  * asked in turn whether it recorded that ray — the coverage definition above — and only the sources that did are sampled.
  *
- * Definition.  num_samples is 1.  All arithmetic is binary32, un-fused, in the order written; min(a, b) is (b < a) ? b : a.
+ * Definition.  num_samples is 1 (lrp_compose_ss_device below takes num_samples).  All arithmetic is binary32, un-fused, in the order written; min(a, b) is (b < a) ? b : a.
  * For output pixel (x, y) and source i: vx, vy, vz is the pixel's target ray after rotation i (rotations + 9 * i; the rotation
  * and the operations of lrp_reproject_device(ins + i, out, 1, ..., rotations + 9 * i); rotations == NULL: no source is rotated,
  * no multiplication happens), sx, sy the coordinates that source's sampler would receive.  Source i COVERS the pixel iff that
@@ -330,6 +330,44 @@ typedef enum lrp_compose_mode { LRP_COMPOSE_FIRST = 0, LRP_COMPOSE_MEAN = 1, LRP
 int lrp_compose_device(const lrp_image *ins, int n_in, const float *rotations /* n_in x 9, or NULL */, const lrp_image *out,
                        int interpolation, int mode, const lrp_post *post, uint8_t *count /* out->width * out->height bytes, or NULL */,
                        int device, void *stream);
+
+/* ---- compose, supersampled: anti-aliased stitching in one launch ------------------------ */
+
+/* lrp_compose_device with num_samples: several large frames composed into a smaller panorama (the reference's --scale 0.5
+ * --samples 2 job, and likewise 3 and 4), one kernel launch per group of 8 channels.  Which sources cover a point is decided
+ * per sub-sample, not per pixel.
+ *
+ * Definition.  All arithmetic is binary32, un-fused, in the order written.  n = num_samples, 1 .. 15.
+ * Sub-sample (ssx, ssy), 0 <= ssx, ssy < n, of output pixel (x, y) sits where an n-sample lrp_reproject_device /
+ * lrp_coverage_device call puts it: scx = cx + ((float)ssx + 1.0f) / ((float)n + 1.0f) - 0.5f with cx the pixel centre in
+ * image-centred coordinates (src/reproject.cpp:287-298), scy likewise.  Sub-samples are numbered j = ssx * n + ssy (ssx the
+ * outer loop, ssy the inner: the reference's loop order).  For sub-sample j: the target ray; per source i rotation i, sx, sy,
+ * covered / not covered by the coverage definition, s_i and (FEATHER) w_i — all exactly as the compose definition above does
+ * for its single sub-sample.  k_j is the number of sources that cover sub-sample j; v_j its composed value under `mode`
+ * (FIRST / MEAN / FEATHER as defined for lrp_compose_device), +0.0f in every channel when k_j == 0.  m is the number of
+ * sub-samples with k_j >= 1.  acc_c = +0.0f; for ascending j with k_j >= 1: acc_c = acc_c + v_j,c.  m == 0: the pixel is +0.0f
+ * in every channel, whatever post is.  Otherwise r = 1.0f / (float)m and the pixel is acc_c * r (with m == n * n the
+ * reference's normalize multiply, :280,338-341), then post on the first min(C, 3) channels.  Dividing by the covered sub-samples
+ * rather than by n * n keeps edges and seams from fading to black; a caller who wants premultiplied edges multiplies by
+ * coverage / (n * n).
+ *   count     device pointer of any alignment, or NULL: per pixel the number of sources that cover at least one of its sub-samples;
+ *   coverage  device pointer of any alignment, or NULL: per pixel m, 0 .. n * n.
+ * Both planes are out->width * out->height bytes, row-major, unpadded.  With more than 8 channels there is one launch per group
+ * of 8, and each writes the planes, with the same bytes.
+ *
+ * Relations:
+ *   n == 1: the bytes of lrp_compose_device, except that a -0.0f channel becomes +0.0f (the accumulation starts from +0.0f);
+ *           count is equal; coverage is k > 0.
+ *   One source, FIRST or MEAN, a pixel with m == n * n: bit for bit what lrp_reproject_device(ins, out, n, interpolation,
+ *           rotation) stores.
+ *
+ * Asynchronous on `stream`; allocates nothing, does not synchronise, builds no lens table, neither reads nor writes the geometry
+ * cache.  Errors, all before a device is touched: those of lrp_compose_device in its order (interpolation 0 .. 2 only, one source
+ * mode for all sources), then LRP_ERR_BAD_ARG for num_samples < 1 or > 15. */
+int lrp_compose_ss_device(const lrp_image *ins, int n_in, const float *rotations /* n_in x 9, or NULL */, const lrp_image *out,
+                          int num_samples, int interpolation, int mode, const lrp_post *post,
+                          uint8_t *count /* out->width * out->height bytes, or NULL */,
+                          uint8_t *coverage /* out->width * out->height bytes, or NULL */, int device, void *stream);
 
 /* ---- one source, several outputs, several GPUs (BASELINE configs[4]) ---------- */
 
