@@ -40,12 +40,30 @@ class LrpPost(ctypes.Structure):
     _fields_ = [("exposure", ctypes.c_float), ("reinhard", ctypes.c_float)]
 
 
+class LrpCamera(ctypes.Structure):
+    """lrp_camera (include/lrp.h "compose, calibrated cameras"), 64 bytes."""
+
+    _fields_ = [
+        ("model", ctypes.c_int32),
+        ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("data", ctypes.c_void_p),
+        ("fx", ctypes.c_float),
+        ("fy", ctypes.c_float),
+        ("cx", ctypes.c_float),
+        ("cy", ctypes.c_float),
+        ("k", ctypes.c_float * 5),
+        ("limit", ctypes.c_float),
+    ]
+
+
 class LrpGeometryCacheInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("bytes", "max_bytes", "entries", "fills", "hits", "bypasses", "evictions")]
 
 
 assert ctypes.sizeof(LrpLens) == 28
 assert ctypes.sizeof(LrpImage) == 56
+assert ctypes.sizeof(LrpCamera) == 64
 
 # Every symbol include/lrp.h declares: (restype, argtypes)
 _P = ctypes.POINTER
@@ -107,6 +125,12 @@ SYMBOLS = {
         [_P(LrpImage), ctypes.c_int, _FLOATP, _P(LrpImage), ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(LrpPost), ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
     ),
+    "lrp_compose_cameras_device": (
+        ctypes.c_int,
+        [_P(LrpCamera), ctypes.c_int, _FLOATP, _P(LrpImage), ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(LrpPost), ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
+    ),
+    "lrp_camera_limit": (ctypes.c_int, [_P(LrpCamera), _P(ctypes.c_float)]),
     "lrp_reproject_multi": (
         ctypes.c_int,
         [_P(LrpImage), _P(LrpImage), ctypes.c_int, ctypes.c_int, ctypes.c_int, _FLOATP, _P(LrpPost), _P(ctypes.c_int), ctypes.c_int],

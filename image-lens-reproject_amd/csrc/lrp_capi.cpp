@@ -2,7 +2,7 @@
 // reference's dispatch order, kernel-argument construction, device buffers,
 // streams and the batch context.  Host code only; the kernels live in the
 // lrp_kernels_*.hip / lrp_tile_*.hip / lrp_eqs_*.hip / lrp_stg_*.hip (reprojection), lrp_tables.hip, lrp_geo_lists.hip,
-// lrp_coverage.hip (coverage planes), lrp_compose*.hip (compose), lrp_packed*.hip (packed pixels), lrp_lanczos*.hip (the Lanczos-3 sampler), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
+// lrp_coverage.hip (coverage planes), lrp_compose*.hip (compose), lrp_camera*.hip (compose, calibrated cameras), lrp_packed*.hip (packed pixels), lrp_lanczos*.hip (the Lanczos-3 sampler), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/lrp.h"
+#include "lrp_camera.h"
 #include "lrp_compose.h"
 #include "lrp_compose_packed.h"
 #include "lrp_compose_ss.h"
@@ -50,6 +51,8 @@ __attribute__((weak)) hipError_t launch_coverage(KParams P, int out_lens, int in
 __attribute__((weak)) hipError_t launch_compose(const ComposeParams &P, int out_lens, int in_mode, int interpolation, hipStream_t stream);
 // lrp_compose_ss.hip, weak like launch_compose (enqueue_compose_ss).
 __attribute__((weak)) hipError_t launch_compose_ss(const ComposeSsParams &P, int out_lens, int in_mode, int interpolation, hipStream_t stream);
+// lrp_camera.hip, weak like launch_compose (enqueue_compose_cameras).
+__attribute__((weak)) hipError_t launch_compose_cameras(const CameraParams &P, int out_lens, int interpolation, hipStream_t stream);
 // lrp_packed.hip, weak like launch_coverage (enqueue_packed).
 __attribute__((weak)) hipError_t launch_packed(PackedParams P, int in_format, int out_lens, int in_mode, int interpolation, int device, hipStream_t stream);
 // lrp_compose_packed.hip, weak like launch_coverage (enqueue_compose_packed).
@@ -703,6 +706,94 @@ int enqueue_compose_ss(const lrp_image *ins, int n_in, const float *rotations, c
   return LRP_OK;
 }
 
+static_assert((int)lrp::kCameraBrown == LRP_CAMERA_BROWN && (int)lrp::kCameraFisheye == LRP_CAMERA_FISHEYE, "lrp_camera.h numbers camera models like include/lrp.h");
+
+// The coefficients of a camera's radial polynomial x * (1 + c[0] x^2 + c[1] x^4 + c[2] x^6 + c[3] x^8): x is r (BROWN: k1 k2 k3) or
+// theta (FISHEYE: k1 .. k4).  Returns how many of cam->k the model uses.
+int camera_radial(const lrp_camera &cam, double c[4]) {
+  if (cam.model == LRP_CAMERA_FISHEYE) {
+    for (int j = 0; j < 4; ++j) c[j] = cam.k[j];
+    return 4;
+  }
+  c[0] = cam.k[0], c[1] = cam.k[1], c[2] = cam.k[4], c[3] = 0.0;
+  return 5;
+}
+
+// lrp_compose_cameras_device's checks, in the order include/lrp.h states.
+int validate_compose_cameras(const lrp_camera *cams, int n_in, const lrp_image *out, int num_samples, int interpolation, int mode) {
+  if (n_in < 1 || n_in > LRP_COMPOSE_MAX_SOURCES)
+    return fail(LRP_ERR_BAD_ARG, "n_in of a compose call must be 1 .. " + std::to_string(LRP_COMPOSE_MAX_SOURCES));
+  if (mode != LRP_COMPOSE_FIRST && mode != LRP_COMPOSE_MEAN && mode != LRP_COMPOSE_FEATHER) return fail(LRP_ERR_BAD_ARG, "unknown compose mode");
+  if (!cams || !out) return fail(LRP_ERR_NULL, cams ? "null image" : "null camera array");
+  if (!lens_in_hot_path(out->lens.type, g_lens_ext.load(std::memory_order_relaxed))) return fail(LRP_ERR_OUTPUT_LENS, "Output lens type not supported.");
+  if (out->channels < 1) return fail(LRP_ERR_CHANNELS, "out->channels must be >= 1");
+  if (out->width < 1 || out->height < 1) return fail(LRP_ERR_BAD_DIMS, "image dimensions must be positive");
+  if (!image_addressable(*out)) return fail(LRP_ERR_BAD_DIMS, "an image of more than 2^31 floats (8 GiB) cannot be addressed");
+  if (!out->data) return fail(LRP_ERR_NULL, "null image data");
+  if (interpolation != LRP_NEAREST && interpolation != LRP_BILINEAR && interpolation != LRP_BICUBIC)
+    return fail(LRP_ERR_INTERPOLATION, "Interpolation method not supported.");
+  for (int i = 0; i < n_in; ++i) {
+    const lrp_camera &cam = cams[i];
+    const std::string who = "camera " + std::to_string(i) + ": ";
+    if (cam.model != LRP_CAMERA_BROWN && cam.model != LRP_CAMERA_FISHEYE) return fail(LRP_ERR_BAD_ARG, who + "unknown model");
+    if (cam.width < 1 || cam.height < 1) return fail(LRP_ERR_BAD_DIMS, who + "width and height must be positive");
+    if ((unsigned long long)cam.width * (unsigned long long)cam.height * (unsigned long long)out->channels > kMaxImageFloats)
+      return fail(LRP_ERR_BAD_DIMS, who + "a frame of more than 2^31 floats (8 GiB) cannot be addressed");
+    if (!cam.data) return fail(LRP_ERR_NULL, who + "data is null");
+    const float intrinsics[4] = {cam.fx, cam.fy, cam.cx, cam.cy};
+    static const char *const names[4] = {"fx", "fy", "cx", "cy"};
+    for (int j = 0; j < 4; ++j)
+      if (!std::isfinite(intrinsics[j])) return fail(LRP_ERR_BAD_ARG, who + names[j] + " is not finite");
+    double c[4];
+    const int used = camera_radial(cam, c);
+    for (int j = 0; j < used; ++j)
+      if (!std::isfinite(cam.k[j])) return fail(LRP_ERR_BAD_ARG, who + "k[" + std::to_string(j) + "] is not finite");
+    if (cam.fx == 0.0f) return fail(LRP_ERR_BAD_ARG, who + "fx must not be 0");
+    if (cam.fy == 0.0f) return fail(LRP_ERR_BAD_ARG, who + "fy must not be 0");
+    if (!(cam.limit >= 0.0f)) return fail(LRP_ERR_BAD_ARG, who + "limit must be >= 0 (+inf allowed)");
+  }
+  if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
+    return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
+  return LRP_OK;
+}
+
+// One launch of the camera compose kernel per group of 8 channels (lrp_camera.hip), each of which writes the planes; no table, no
+// geometry-cache entry, no allocation.
+int enqueue_compose_cameras(const lrp_camera *cams, int n_in, const float *rotations, const lrp_image *out, int num_samples, int interpolation,
+                            int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, hipStream_t stream) {
+  if (!lrp::launch_compose_cameras) return fail(LRP_ERR_HIP, "the camera compose kernels (lrp_camera.hip) are not part of this build");
+  lrp::CameraParams C;
+  std::memset(&C, 0, sizeof(C));
+  C.out_w = out->width, C.out_h = out->height, C.channels = out->channels;
+  C.out_lens = pack_lens(out->lens);
+  if (post) C.exposure = post->exposure, C.reinhard = post->reinhard;
+  for (int i = 0; i < n_in; ++i) {
+    lrp::CameraSource &S = C.src[i];
+    S.in_w = cams[i].width, S.in_h = cams[i].height;
+    S.model = cams[i].model;
+    S.fx = cams[i].fx, S.fy = cams[i].fy, S.cx = cams[i].cx, S.cy = cams[i].cy;
+    std::memcpy(S.k, cams[i].k, sizeof(S.k));
+    S.limit = cams[i].limit;
+    S.has_rot = rotations != nullptr;
+    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
+  }
+  C.n_src = n_in;
+  C.mode = mode;
+  C.num_samples = num_samples;
+  C.count = count;
+  C.coverage = coverage;
+  const int channels = out->channels, group = lrp::kComposeMaxChannels;
+  for (int c0 = 0; c0 < channels; c0 += group) {
+    for (int i = 0; i < n_in; ++i) C.src[i].data = cams[i].data + c0;
+    C.dst = out->data + c0;
+    C.ch_count = std::min(group, channels - c0);
+    C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
+    const hipError_t e = lrp::launch_compose_cameras(C, out->lens.type, interpolation, stream);
+    if (e != hipSuccess) return hip_fail(e, "camera compose kernel launch");
+  }
+  return LRP_OK;
+}
+
 static_assert((int)lrp::kPackedF32 == LRP_PIXEL_F32 && (int)lrp::kPackedF16 == LRP_PIXEL_F16 && (int)lrp::kPackedU8 == LRP_PIXEL_U8_GAMMA, "lrp_packed.h numbers pixel formats like include/lrp.h");
 
 bool format_ok(int f) { return f == LRP_PIXEL_F32 || f == LRP_PIXEL_F16 || f == LRP_PIXEL_U8_GAMMA; }
@@ -1015,6 +1106,59 @@ int lrp_compose_ss_device(const lrp_image *ins, int n_in, const float *rotations
   st = select_device(device);
   if (st != LRP_OK) return st;
   return enqueue_compose_ss(ins, n_in, rotations, out, num_samples, interpolation, mode, post, count, coverage, (hipStream_t)stream);
+}
+
+int lrp_compose_cameras_device(const lrp_camera *cams, int n_in, const float *rotations, const lrp_image *out, int num_samples,
+                               int interpolation, int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, int device, void *stream) {
+  int st = validate_compose_cameras(cams, n_in, out, num_samples, interpolation, mode);
+  if (st != LRP_OK) return st;
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_compose_cameras(cams, n_in, rotations, out, num_samples, interpolation, mode, post, count, coverage, (hipStream_t)stream);
+}
+
+// Host only, in double.  g(x) = x * (1 + c0 x^2 + c1 x^4 + c2 x^6 + c3 x^8) is scanned upwards in steps of h while it increases; the
+// step that stops increasing brackets the turning point between the sample before it and the sample after it, and the root of g'
+// in that bracket is closed in on by bisection from below, so that the result never exceeds the turning point.
+int lrp_camera_limit(const lrp_camera *cam, float *limit) {
+  if (!cam || !limit) return fail(LRP_ERR_NULL, "null camera or limit");
+  if (cam->model != LRP_CAMERA_BROWN && cam->model != LRP_CAMERA_FISHEYE) return fail(LRP_ERR_BAD_ARG, "unknown camera model");
+  double c[4];
+  const int used = camera_radial(*cam, c);
+  for (int j = 0; j < used; ++j)
+    if (!std::isfinite(cam->k[j])) return fail(LRP_ERR_BAD_ARG, "k[" + std::to_string(j) + "] is not finite");
+  const bool brown = cam->model == LRP_CAMERA_BROWN;
+  const double x_max = brown ? 16.0 : M_PI;
+  const int steps = brown ? 16 * 1024 : 4096;
+  const double h = x_max / steps;
+  const auto g = [&](double x) {
+    const double x2 = x * x;
+    return x * (1.0 + x2 * (c[0] + x2 * (c[1] + x2 * (c[2] + x2 * c[3]))));
+  };
+  const auto dg = [&](double x) {
+    const double x2 = x * x;
+    return 1.0 + x2 * (3.0 * c[0] + x2 * (5.0 * c[1] + x2 * (7.0 * c[2] + x2 * (9.0 * c[3]))));
+  };
+  int j = 0;
+  while (j < steps && g((j + 1) * h) > g(j * h)) ++j;
+  if (j == steps) { // increases all the way
+    *limit = brown ? INFINITY : (float)M_PI; // (the float atan2f returns for the ray straight backwards)
+    return LRP_OK;
+  }
+  double lo = j > 0 ? (j - 1) * h : 0.0, hi = (j + 1) * h; // g' > 0 at lo (or lo == 0, where g' == 1); the turning point is in [lo, hi]
+  if (dg(lo) > 0.0 && !(dg(hi) > 0.0))
+    for (int it = 0; it < 64; ++it) {
+      const double mid = 0.5 * (lo + hi);
+      if (dg(mid) > 0.0)
+        lo = mid;
+      else
+        hi = mid;
+    }
+  const double v = brown ? lo * lo : lo;
+  float f = (float)v;
+  if ((double)f > v) f = std::nextafter(f, 0.0f); // round down
+  *limit = f;
+  return LRP_OK;
 }
 
 int lrp_reproject_packed_device(const lrp_image *in, int in_format, int in_packed_channels, lrp_image *out, int out_format,

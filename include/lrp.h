@@ -369,6 +369,76 @@ int lrp_compose_ss_device(const lrp_image *ins, int n_in, const float *rotations
                           uint8_t *count /* out->width * out->height bytes, or NULL */,
                           uint8_t *coverage /* out->width * out->height bytes, or NULL */, int device, void *stream);
 
+/* ---- compose, calibrated cameras: Brown-Conrady and fisheye polynomials ------------------ */
+
+/* lrp_compose_ss_device for the frames of real cameras.  The sources of the two compose calls above are ideal lenses: the
+ * optical axis in the centre of the frame, one focal length, no distortion.  A calibration delivers fx, fy, cx, cy in pixels
+ * and distortion coefficients; both common models are closed-form polynomials in the direction this library needs — from ray
+ * to source pixel —, so a calibrated frame is composed as it is, without an undistorted copy.  Undistorting one image is the
+ * n_in == 1 case: a calibrated source into a rectilinear target.
+ *
+ * Definition.  Everything is the definition of lrp_compose_ss_device — sub-sample positions and order, FIRST / MEAN / FEATHER,
+ * m, the 1.0f / (float)m normalisation, post, both planes, one launch per group of 8 channels — with two things replaced, for
+ * camera i and the ray vx, vy, vz after rotation i: the source coordinates sx, sy and the coverage test.  Binary32, un-fused,
+ * in the order written; k1 .. are the camera's k[]:
+ *   LRP_CAMERA_BROWN (Brown-Conrady, k = k1 k2 p1 p2 k3: OpenCV's order)
+ *     a = vx / -vz;  b = vy / -vz;  r2 = a*a + b*b;  ab = a*b;
+ *     L  = 1.0f + r2*(k1 + r2*(k2 + r2*k3));
+ *     xd = a*L + ((2.0f*p1)*ab + p2*(r2 + 2.0f*(a*a)));
+ *     yd = b*L + (p1*(r2 + 2.0f*(b*b)) + (2.0f*p2)*ab);
+ *     sx = fx*xd + cx;  sy = fy*yd + cy;                      imaged = vz < 0.0f && r2 <= limit
+ *   LRP_CAMERA_FISHEYE (Kannala-Brandt, k = k1 k2 k3 k4: the order of OpenCV's fisheye module; k[4] is ignored)
+ *     rho = sqrtf(vx*vx + vy*vy);  theta = atan2f(rho, -vz);  t2 = theta*theta;
+ *     td  = theta*(1.0f + t2*(k1 + t2*(k2 + t2*(k3 + t2*k4))));
+ *     q   = (rho > 0.0f) ? td / rho : 0.0f;
+ *     sx  = fx*(q*vx) + cx;  sy = fy*(q*vy) + cy;             imaged = theta <= limit
+ * A sub-sample is COVERED by camera i iff imaged && sx >= -0.5f && sx <= (float)width - 0.5f && sy >= -0.5f &&
+ * sy <= (float)height - 0.5f, comparisons with NaN being false.  s_i is sample<interpolation> at (sx, sy), clamping and never
+ * wrapping; FEATHER's dx, dy, w_i are those of the compose definition (m = min(dx, dy)).
+ * Axes: the library's — x right, y down, the camera looks down -z; OpenCV's camera frame with z_cv = -vz.  (0, 0) is the
+ * CENTRE of the top-left texel, as in the samplers' sx, sy and in OpenCV.  The fisheye takes the angle from atan2f, not from a
+ * fold through x / -z: a camera that sees behind itself (190 - 220 degree lenses) is expressible, with limit up to pi.
+ * limit exists because both polynomials stop being monotonic off axis: without it, rays far outside the field of view fold
+ * back into the frame as ghosts.  +inf is allowed.  The models may be mixed in one call.
+ *
+ * lrp_camera_limit (host only, evaluated in double): BROWN: the r2 = r * r of the last r on an ascending scan for which
+ * g(r) = r * L(r * r) still increases (the tangential terms do not enter); +inf when g increases up to r = 16.  FISHEYE: the
+ * last theta for which td(theta) still increases; (float)pi when it does so up to pi.  The scan steps by 1 / 1024 (BROWN) or
+ * pi / 4096 (FISHEYE); the step at which the function stops increasing brackets the turning point, and the bracket is then
+ * bisected on the sign of the derivative, keeping the lower end where it is positive.  When a turning point t exists (for BROWN
+ * t is the r2 at the turning point), the result v satisfies 0.99 * t <= v <= t; v is rounded down to float.  cam->data,
+ * width, height, fx, fy, cx, cy and limit are not looked at.  Errors: cam or limit NULL: LRP_ERR_NULL; an unknown model or a
+ * used coefficient that is not finite: LRP_ERR_BAD_ARG.
+ *
+ * lrp_compose_cameras_device: asynchronous on `stream`; allocates nothing, does not synchronise, builds no lens table, neither
+ * reads nor writes the geometry cache (the lrp_geometry_cache_stats counters do not move).  Errors, all before a device is
+ * touched, in this order:
+ *   1. n_in outside 1 .. LRP_COMPOSE_MAX_SOURCES or an unknown mode: LRP_ERR_BAD_ARG;
+ *   2. cams or out NULL: LRP_ERR_NULL;
+ *   3. the output-side checks of lrp_compose_ss_device: the output lens and its extension bit (LRP_ERR_OUTPUT_LENS),
+ *      out->channels < 1 (LRP_ERR_CHANNELS), a non-positive size or more than 2^31 floats (LRP_ERR_BAD_DIMS), out->data NULL
+ *      (LRP_ERR_NULL);
+ *   4. interpolation outside 0 .. 2: LRP_ERR_INTERPOLATION;
+ *   5. per camera, ascending: an unknown model: LRP_ERR_BAD_ARG; a non-positive size or more than 2^31 floats
+ *      (width * height * out->channels): LRP_ERR_BAD_DIMS; data NULL: LRP_ERR_NULL; fx, fy, cx, cy or a used k not finite, fx or
+ *      fy equal to 0, or limit NaN or negative: LRP_ERR_BAD_ARG with an lrp_last_error text that names the camera index and the
+ *      field ("camera 2: k[1] ...");
+ *   6. num_samples outside 1 .. 15: LRP_ERR_BAD_ARG. */
+typedef enum lrp_camera_model { LRP_CAMERA_BROWN = 0, LRP_CAMERA_FISHEYE = 1 } lrp_camera_model;
+typedef struct lrp_camera {
+  int32_t model;          /* lrp_camera_model */
+  int32_t width, height;  /* the frame; it has out->channels channels */
+  const float *data;      /* device pointer, interleaved float32 like lrp_image */
+  float fx, fy, cx, cy;   /* pixels; (0, 0) is the CENTRE of the top-left texel */
+  float k[5];             /* BROWN: k1 k2 p1 p2 k3.  FISHEYE: k1 k2 k3 k4, k[4] ignored */
+  float limit;            /* BROWN: largest r2 that is imaged; FISHEYE: largest theta (radians).  +inf allowed */
+} lrp_camera;
+int lrp_compose_cameras_device(const lrp_camera *cams, int n_in, const float *rotations /* n_in x 9, or NULL */,
+                               const lrp_image *out, int num_samples, int interpolation, int mode, const lrp_post *post,
+                               uint8_t *count /* out->width * out->height bytes, or NULL */,
+                               uint8_t *coverage /* out->width * out->height bytes, or NULL */, int device, void *stream);
+int lrp_camera_limit(const lrp_camera *cam, float *limit);
+
 /* ---- one source, several outputs, several GPUs (BASELINE configs[4]) ---------- */
 
 /* One host source, n_out host outputs (lenses in outs[i].lens, rotations + 9 * i or none): the
