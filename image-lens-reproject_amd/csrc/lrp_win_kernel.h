@@ -60,6 +60,19 @@ constexpr int frame_loop_hoist(int in_mode, int ch) {
 constexpr bool frame_loop_grouped_lanes(int in_mode, int ch) {
   return in_mode == kInEquidistant && ch == 4;
 }
+// Which of those kernels dispatch on the tier of their block ONCE, in front of the frame loop: a block of the coefficient tier
+// (whole-block or half-block planes) then runs a frame loop of its own — the wait, precompute(), four passes without a tier
+// test, the request of the next frame's window — and the generic loop of the other tiers (raw taps, edge row / column,
+// corner, gathers) is compiled without the coefficient tier.  The tier of the one block is the same in every frame; tested
+// per pass it cost every pass of every frame the flag tests and four to five taken branches over the other tiers' bodies.
+// All twelve take it: no 16-frame kbench row of theirs is slower for it than the parent's own spread
+// (profiles/r11_frame_loop_tier_dispatch.txt section 5).  The arguments are the opt-out hook, like frame_loop_grouped_lanes':
+// an instantiation that comes to lose by the dispatch keeps the one generic loop by returning false for it here.
+constexpr bool frame_loop_tier_dispatch(int in_mode, int ch) {
+  (void)in_mode;
+  (void)ch;
+  return true;
+}
 // an LDS byte address (a multiple of the size of T) as a pointer; the reads through it are ds_read: the address space is inferred from the cast
 template <class T> __device__ __forceinline__ const T *lds_ptr(uint32_t byte_addr) {
   return static_cast<const T *>(__builtin_assume_aligned((const T *)(__attribute__((address_space(3))) const T *)(uintptr_t)byte_addr, sizeof(T)));
@@ -1321,8 +1334,103 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
       }
     }
   }
+  // The one-block frame-loop kernels dispatch on the tier here, once (frame_loop_tier_dispatch above): a block of the
+  // coefficient tier takes coef_frames() below, every other tier the generic loop — compiled without the coefficient tier.
+  constexpr bool kCoefLoop = kOneBlock && kCoefHere && frame_loop_tier_dispatch(InMode, CH);
+  // The next frame's window of the one block, requested from the coefficient tier's own loop: issue()'s staged rows with
+  // fewer scalar instructions per row.  M0 and the row's address are running scalars (M0 is advanced behind the request that
+  // read it: the two adds of the address stand between its write and the next request, which is the wait state the pair
+  // needs), the end of the window's LDS rows — the same in every frame — ends the loop: no counter, and two rows per trip.
+  // 5 instructions per window row where the loop of issue() spends 9.  A staged window has bh >= 4 rows (lrp_win_plan.h: the
+  // four tap rows of one source row at the least), so after the odd row there are always rows left for the pairs.
+  // (The row's address sits in a named register pair, s[100:101]: the 64-bit add needs the names of its halves, which an
+  // operand the compiler places does not give.  Both halves are written by scalar adds, so the request that reads them has no
+  // wait state to keep; M0's is kept by the two instructions between its s_mov and the first request.)
+  // (RGBAZ requests a colour row and a depth row per window row, two running LDS addresses: it keeps issue().)
+  auto request_next_frame = [&](const float *frame) {
+    if constexpr (CH == 5) {
+      issue(frame, cur);
+    } else {
+      // the reads of the window issued so far have returned before anything overwrites it
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (lane < cur.bw) {
+        const uint32_t lane_bytes = (uint32_t)(cur.x_lo + lane) * (4u * CH);
+        uint64_t row = reinterpret_cast<uint64_t>(frame) + (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)cur.y_lo * src.row_bytes)); // wave-uniform
+        const uint32_t lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds0);
+        const uint32_t lds_step = (uint32_t)__builtin_amdgcn_readfirstlane(cur.pitch * 16); // dwordx3 too writes one 16-byte slot per lane
+        const uint32_t lds_end = lds + (uint32_t)__builtin_amdgcn_readfirstlane(cur.bh) * lds_step;
+        const uint32_t row_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)src.row_bytes);
+#define LRP_REQUEST_ROW(LOAD)                                                                                                   \
+  LOAD " %[voff], s[100:101]\n\ts_add_u32 m0, m0, %[step]\n\ts_add_u32 s100, s100, %[rb]\n\ts_addc_u32 s101, s101, 0\n\t"
+#define LRP_REQUEST_ROWS(LOAD)                                                                                                  \
+  "s_mov_b32 m0, %[lds]\n\ts_bitcmp0_b32 %[rows], 0\n\ts_cbranch_scc1 .Lrows%=\n\t" LRP_REQUEST_ROW(LOAD) ".Lrows%=:\n\t"     \
+  LRP_REQUEST_ROW(LOAD) LRP_REQUEST_ROW(LOAD) "s_cmp_lt_u32 m0, %[end]\n\ts_cbranch_scc1 .Lrows%="
+        if constexpr (CH == 3)
+          asm volatile(LRP_REQUEST_ROWS("global_load_lds_dwordx3")
+                       : "+{s[100:101]}"(row)
+                       : [voff] "v"(lane_bytes), [lds] "s"(lds), [step] "s"(lds_step), [end] "s"(lds_end), [rb] "s"(row_bytes), [rows] "s"(__builtin_amdgcn_readfirstlane(cur.bh))
+                       : "memory", "m0", "scc");
+        else
+          asm volatile(LRP_REQUEST_ROWS("global_load_lds_dwordx4")
+                       : "+{s[100:101]}"(row)
+                       : [voff] "v"(lane_bytes), [lds] "s"(lds), [step] "s"(lds_step), [end] "s"(lds_end), [rb] "s"(row_bytes), [rows] "s"(__builtin_amdgcn_readfirstlane(cur.bh))
+                       : "memory", "m0", "scc");
+#undef LRP_REQUEST_ROWS
+#undef LRP_REQUEST_ROW
+      }
+    }
+  };
+  // The coefficient tier's frame loop: per frame the wait for the window, precompute() (a second time for the second half
+  // where the planes of the whole block do not fit), four passes — the reads, the arithmetic and the store of the generic
+  // loop's coefficient tier, in its order — and, behind the `b` reads of pass 3 and ahead of its arithmetic and store, the
+  // request of the next frame's window.  What is tested per frame is scalar: the planes' extent, the last frame, the tonemap
+  // (in the store).  The destination of frame f and the source of frame f + 1 are fetched where frame f starts, in front of
+  // the wait for its window: both have arrived when precompute() has waited for its first LDS reads, and pass 3 requests
+  // the next window without a round trip through the scalar cache of its own.
+  auto coef_frames = [&]() {
+    // (a launch of these kernels is a batch — P.frames_per_wave > 1 is what selects them, win_kernel() below — so the frames'
+    // pointers are the batch arrays': no select between them and the single launch's pair)
+    auto frame_pointers = [&](int f) {
+      P.dst = Pk.batch_dst[frame0 + f];
+      return Pk.batch_src[frame0 + min(f + 1, n_frames - 1)]; // (the last frame requests nothing: any valid entry)
+    };
+    const float *next_src = frame_pointers(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the window was the last thing requested
+    int f = 0;
 #pragma unroll 1
-  for (int g = 0; g < G; ++g) {
+    for (;;) {
+      // (see the generic loop: what precompute() and the request derive per lane from the block record is not to be held
+      // across the frames, and the flags of the record are scalar compares of an opaque copy)
+      asm volatile("" : "+v"(lane));
+      int tier = __builtin_amdgcn_readfirstlane(cur.tier);
+      asm volatile("" : "+s"(tier));
+#if defined(LRP_TIER_STATS)
+      if (lane == 0) atomicAdd(&g_tier_stats[0], 1u);
+#endif
+      const bool more = f + 1 < n_frames;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int h = k >> 1;
+        if (k == 0 || (k == 2 && (tier & 4) == 0)) precompute(cur, h);
+        asm volatile("" : "+v"(pl[k].a), "+v"(pl[k].b), "+v"(pl[k].addr));
+        if constexpr (kHoist >= 2) asm volatile("" : "+v"(pl[k].dst));
+        const PassLane q = pl[k];
+        const Rgba s = win_tier_coef<CH>(lds_ptr<float4>(q.addr), lds_ptr<float4>(q.addr + (uint32_t)(cur.c_delta(h) * 16)), cur.c_plane, cur.pitch,
+                                         lds_ptr<float>((q.addr >> 2) + (lds0 - (lds0 >> 2)) + (uint32_t)(cur.pitch * cur.bh * 16 - cur.spitch() * 4)), q.a, q.b, [&]() {
+                                           if (k == 3 && more) request_next_frame(next_src);
+                                         });
+        emit(0, k, s, std::integral_constant<bool, kRunsEverywhere>{}, P.rgbaz_runs != 0);
+      }
+      if (++f >= n_frames) break;
+      next_src = frame_pointers(f);
+      asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); // the window has landed; the store of pass 3 may be in flight
+    }
+  };
+  bool coef_block = false;
+  if constexpr (kCoefLoop) coef_block = cur.coef() != 0; // (scalar: the record was made uniform above)
+  if (coef_block) coef_frames();
+#pragma unroll 1
+  for (int g = 0; g < (coef_block ? 0 : G); ++g) {
    g_loop = g;
    // plain blocks: the next block's coordinates here, long before its window is requested in the
    // last pass; mirrored blocks derive theirs in a few instructions right there (fewer live registers)
@@ -1357,7 +1465,8 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
     // (kHoist: the block record is scalar and the same in every frame — the flags below from an opaque copy made per frame
     // are scalar compares; hoisted out of the frame loop as lane masks they come back through v_cndmask / v_cmp)
     if constexpr (kHoist >= 1) asm volatile("" : "+s"(tier));
-    const bool t_coef = kCoefHere && (tier & 2) != 0, t_staged = (tier & 1) != 0, t_whole = (tier & 4) != 0;
+    // (kCoefLoop: a block of the coefficient tier never gets here — coef_frames() — and the tier is not compiled into this loop)
+    const bool t_coef = kCoefHere && !kCoefLoop && (tier & 2) != 0, t_staged = (tier & 1) != 0, t_whole = (tier & 4) != 0;
     const int t_edge = kEdge ? ((tier >> 6) & 7) : 0;
     const bool t_split = kSplit && (tier & 512) != 0; // the window holds passes 0-1; that of passes 2-3 is fetched behind pass 1's taps // 1, 2: beyond the first / last source row; 3, 4: column
 #if defined(LRP_TIER_STATS)

@@ -8,6 +8,11 @@
   isa_kernels.py passes <obj-dir> <symbol>  the coefficient-tier and raw-tap pass bodies of the window kernel <symbol> (a
                                             substring of its mangled name): per body its tier, ds_read_b128, packed and
                                             non-packed VALU instructions up to the global_store_dwordx4 (coef_passes below)
+  isa_kernels.py frame <obj-dir> <symbol> [--rows N] [--trips M] [--half] [--post]
+                                            the instructions of ONE FRAME of the coefficient-tier frame loop of a one-block
+                                            window kernel, by class: packed, other VALU, LDS, vector memory, scalar, waits,
+                                            branches; the request loop counted for N window rows, precompute() for M trips
+                                            (coef_frame below)
 
 The hash is of the kernel's disassembly without addresses, encodings and comments.  Branch operands are relative; the one
 position-dependent operand, the literal of an s_getpc_b64 / s_add_u32 / s_addc_u32 address computation, is replaced by the
@@ -202,9 +207,139 @@ def coef_passes(listing):
         path = own + tail
         bodies.append({"tier": "coef" if packed < 120 else "raw", "ds_read_b128": sum(t.startswith("ds_read_b128") for t in path),
                        "packed": sum(t.startswith("v_pk_") for t in path), "valu": sum(is_valu(t) for t in path), "lines": len(path),
-                       "valu_text": [t for t in path if is_valu(t)]})
+                       "valu_text": [t for t in path if is_valu(t)], "span": (first, j)})
         i = j + 1
     return bodies
+
+
+CLASSES = ("packed", "other VALU", "LDS", "vector memory", "scalar", "waits", "branches")
+
+
+def instruction_class(t):
+    if t.startswith("v_pk_"):
+        return "packed"
+    if t.startswith("v_"):
+        return "other VALU"
+    if t.startswith("ds_"):
+        return "LDS"
+    if t.startswith(("global_", "buffer_", "flat_", "scratch_")):
+        return "vector memory"
+    if t.startswith(("s_waitcnt", "s_nop")):
+        return "waits"
+    if t.startswith(("s_cbranch", "s_branch", "s_setpc", "s_endpgm")):
+        return "branches"
+    return "scalar"
+
+
+def coef_frame(listing, rows=12, trips=1, whole=True, post=False):
+    """The instructions one wavefront issues for ONE FRAME of a block of the coefficient tier in a one-block frame-loop window
+    kernel, by class (CLASSES) — a static account of the code, made the same way for every build:
+
+      * the frame loop is the innermost loop (a backward branch and its target) around the four coefficient-tier pass bodies
+        of coef_passes();
+      * inside it, every loop (the merged spans of the backward branches) that writes coefficient planes (ds_write_b128) is a
+        precompute() trip loop and counts `trips` times; the loop that requests window rows (global_load_lds_*) counts
+        rows / (requests per trip) times.  A precompute() trip is counted with both of its chunks of 64 origins and the
+        tests around them;
+      * left out: what a FORWARD branch skips when the skipped span holds nothing of the coefficient path — no part of a
+        coefficient-tier body, no precompute() loop: the bodies of the other tiers and the flag tests between them,
+        where the tier is tested per pass, a corner block's stores; the tonemap (a span of arithmetic with v_div_scale_f32
+        and no memory instruction) unless `post` — also where it is not skipped by a forward branch but lies behind a
+        conditional latch of the frame loop, as the fall-through that ends in a latch of its own; with `whole`
+        (planes of the whole block) the second precompute() and what is skipped with it; with an even `rows` the single row
+        requested in front of a loop that requests rows in pairs (the span skipped behind an s_bitcmp0_b32).
+    What is neither multiplied nor left out counts once.  -> ({class: count}, {"loop": (first, last), "left_out": n, ...}) or
+    None when the kernel has no four coefficient-tier bodies inside one loop."""
+    at = {a: i for i, (a, _) in enumerate(listing)}
+    n = len(listing)
+    text = [t for _, t in listing]
+
+    def target(i):
+        off = int(text[i].split()[-1])
+        return at.get(listing[i][0] + 4 + 4 * (off - 65536 if off >= 32768 else off))
+
+    coef = [b["span"] for b in coef_passes(listing) if b["tier"] == "coef"]
+    if len(coef) != 4:
+        return None
+    branches = [(i, target(i)) for i in range(n) if text[i].startswith(("s_cbranch", "s_branch"))]
+    branches = [(i, t) for i, t in branches if t is not None]
+    first_body, last_body = coef[0][0], coef[-1][1]
+    around = [(i, t) for i, t in branches if t <= first_body and i >= last_body]
+    if not around:
+        return None
+    head = max(t for _, t in around)
+    latches = [(i, t) for i, t in around if t > head - 32]  # (a structurized loop may close through two branches to neighbouring blocks)
+    lo, hi = min(t for _, t in latches), max(i for i, _ in latches)
+    # inner loops: merged spans of the backward branches inside the frame loop
+    spans = sorted((t, i) for i, t in branches if lo < t <= i < hi and not (t <= first_body and i >= last_body))
+    loops = []
+    for t, i in spans:
+        if loops and t <= loops[-1][1]:
+            loops[-1][1] = max(loops[-1][1], i)
+        else:
+            loops.append([t, i])
+    weight = [1] * n
+    pre_loops = []
+    for t, i in loops:
+        body = text[t:i + 1]
+        if any(x.startswith("global_load_lds") for x in body) and any(a <= t and i <= b for a, b in coef):  # (the request of a coefficient-tier pass)
+            per_trip = sum(x.startswith("global_load_lds") for x in body)
+            for k in range(t, i + 1):
+                weight[k] = rows // per_trip
+        elif sum(x.startswith("ds_write_b128") for x in body) >= 3:
+            pre_loops.append((t, i))
+            for k in range(t, i + 1):
+                weight[k] = trips
+    hot = [False] * n  # part of the coefficient path for certain
+    for a, b in coef + pre_loops:
+        for k in range(a, b + 1):
+            hot[k] = True
+    left_out = [False] * n
+    for i, t in branches:
+        if not (lo <= i < t <= hi + 1):
+            continue
+        skipped = range(i + 1, t)
+        cold = not any(hot[k] for k in skipped)
+        if cold and any(text[k].startswith("v_div_scale_f32") for k in skipped) and not any(text[k].startswith(("ds_", "global_")) for k in skipped):
+            cold = not post  # the tonemap alone: arithmetic between a pass's sample and its store
+        second = whole and len(pre_loops) >= 2 and any(pre_loops[1][0] <= k <= pre_loops[1][1] for k in skipped) and \
+            not any(a <= k <= b for a, b in coef for k in skipped)
+        odd_row = rows % 2 == 0 and i > 0 and text[i - 1].startswith("s_bitcmp0_b32") and any(text[k].startswith("global_load_lds") for k in skipped)
+        if cold or second or odd_row:
+            for k in skipped:
+                left_out[k] = True
+    # The loop may close through a CONDITIONAL latch with the tonemap of the last pass as its fall-through, ending in a latch
+    # of its own (the parent of the per-tier loop: pass 3 without a tonemap branches back, the tonemap follows): no forward
+    # branch skips that body, the latch in front of it does.
+    order = sorted(i for i, _ in latches)
+    for a, b in zip(order, order[1:]):
+        body = range(a + 1, b + 1)
+        if not post and text[a].startswith("s_cbranch") and any(text[k].startswith("v_div_scale_f32") for k in body) and \
+                not any(hot[k] or text[k].startswith(("ds_", "global_")) for k in body):
+            for k in body:
+                left_out[k] = True
+    counts = {c: 0 for c in CLASSES}
+    for k in range(lo, hi + 1):
+        if not left_out[k]:
+            counts[instruction_class(text[k])] += weight[k]
+    info = {"loop": (lo, hi), "static": hi - lo + 1, "left_out": sum(left_out[lo:hi + 1]), "precompute_loops": len(pre_loops),
+            "rows": rows, "trips": trips, "whole": whole, "post": post}
+    return counts, info
+
+
+def kernel_frame(obj_dir, symbol, only=None, **kw):
+    """coef_frame of the kernel whose mangled name contains `symbol`; None: not found, or no coefficient-tier loop in it."""
+    with tempfile.TemporaryDirectory() as tmp:
+        for name in sorted(os.listdir(obj_dir)):
+            if not name.endswith(".o") or (only is not None and name not in only):
+                continue
+            co = code_object(os.path.join(obj_dir, name), tmp)
+            if co is None:
+                continue
+            listing = kernel_listing(co, symbol)
+            if listing:
+                return coef_frame(listing, **kw)
+    return None
 
 
 def kernel_passes(obj_dir, symbol, only=None):
@@ -279,6 +414,27 @@ def main(argv):
             print(f"pass body {k} ({b['tier']}): ds_read_b128 {b['ds_read_b128']} packed {b['packed']} non-packed VALU {b['valu']} instructions {b['lines']}")
             for t in b["valu_text"]:
                 print("   ", t)
+        return 0
+    if len(argv) >= 4 and argv[1] == "frame":
+        import argparse
+        ap = argparse.ArgumentParser(prog="isa_kernels.py frame")
+        ap.add_argument("obj_dir")
+        ap.add_argument("symbol")
+        ap.add_argument("--rows", type=int, default=12, help="rows of the window (requests of the next frame's window)")
+        ap.add_argument("--trips", type=int, default=1, help="trips of a precompute() loop (128 origins each)")
+        ap.add_argument("--half", action="store_true", help="half-block planes: the second precompute() runs")
+        ap.add_argument("--post", action="store_true", help="the tonemap runs")
+        a = ap.parse_args(argv[2:])
+        r = kernel_frame(a.obj_dir, a.symbol, rows=a.rows, trips=a.trips, whole=not a.half, post=a.post)
+        if r is None:
+            print("no such kernel, or no loop around four coefficient-tier bodies:", a.symbol)
+            return 1
+        counts, info = r
+        print(f"frame loop: instructions {info['loop'][0]}..{info['loop'][1]} of the kernel ({info['static']} static, {info['left_out']} left out), "
+              f"{info['precompute_loops']} precompute() loops; rows {a.rows}, trips {a.trips}, {'half' if a.half else 'whole'}-block planes, tonemap {'on' if a.post else 'off'}")
+        for c in CLASSES:
+            print(f"  {c:14s} {counts[c]:5d}")
+        print(f"  {'per frame':14s} {sum(counts.values()):5d}   per pass {sum(counts.values()) / 4:.1f}")
         return 0
     if len(argv) == 4 and argv[1] == "compare":
         a, bad_a = unique(kernels(argv[2]), "a")
