@@ -20,7 +20,10 @@ compose_ss(in_images, out_image, num_samples, interpolation, ...) does so with
 num_samples^2 sub-samples per pixel (anti-aliased stitching), and
 compose_cameras(cameras, out_image, num_samples, interpolation, ...) takes the
 frames of calibrated cameras (Camera: fx, fy, cx, cy and Brown-Conrady or
-Kannala-Brandt distortion coefficients) instead of ideal lenses.
+Kannala-Brandt distortion coefficients) instead of ideal lenses, and
+camera_view(cameras, target, out, num_samples, interpolation, ...) renders them
+into the frame of another calibrated camera (camera_unproject(camera, uv) is
+the pixel-to-ray inverse it uses, on the host).
 
 The directory name contains a hyphen (it is the name the build contract fixes);
 import it with importlib.import_module("image-lens-reproject_amd").
@@ -533,6 +536,67 @@ def compose_cameras(cameras, out_image, num_samples, interpolation, rotation_mat
     del keep
     _check(st)
     return planes["count"], planes["coverage"]
+
+
+def camera_view(cameras, target, out, num_samples, interpolation, rotation_matrices=None, mode=ComposeMode.FIRST, post=None, count=None,
+                coverage=None, device=None, stream=None):
+    """lrp_camera_view_device (include/lrp.h "calibrated camera as the target"): compose_cameras() into the frame of another
+    calibrated camera — a new camera matrix, camera-to-camera remapping, re-distortion.  target: a Camera whose data is
+    ignored; out: a float32 CUDA tensor of target.height * target.width * channels elements, channels being every camera's.
+    Pixels of the target for which its polynomial has no ray are +0.0 with coverage 0.  Device tensors only; asynchronous on
+    `stream`.  count / coverage and the return value: as compose_cameras()."""
+    import torch
+
+    lib = _native.load()
+    n = len(cameras)
+    px = target.width * target.height
+    if (not _is_torch(out) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or px <= 0 or out.numel() == 0
+            or out.numel() % px != 0):
+        raise ValueError("out must be a contiguous float32 CUDA tensor with height*width*channels elements")
+    channels = out.numel() // px
+    wanted = {}
+    for name, arg in (("count", count), ("coverage", coverage)):
+        wanted[name] = arg is not None and arg is not False
+        if wanted[name] and arg is not True:
+            if not _is_torch(arg) or arg.dtype != torch.uint8 or not arg.is_cuda or not arg.is_contiguous() or arg.numel() != px:
+                raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor with height*width elements")
+    if not all(c.on_device() for c in cameras):
+        raise ValueError("camera_view() takes device tensors only: the data of every camera must be a CUDA tensor")
+    if device is None:
+        device = out.device.index
+    planes = {}
+    for name, arg in (("count", count), ("coverage", coverage)):
+        planes[name] = None
+        if wanted[name]:
+            planes[name] = torch.empty((target.height, target.width), dtype=torch.uint8, device=f"cuda:{device}") if arg is True else arg
+    arr = (_native.LrpCamera * max(n, 1))(*[c.to_c(channels) for c in cameras])
+    ctarget = target.to_c()
+    rot, keep = None, None
+    if rotation_matrices is not None:
+        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
+        rot = keep.ctypes.data
+    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    st = lib.lrp_camera_view_device(arr, n, rot, ctypes.byref(ctarget), out.data_ptr(), channels, int(num_samples), int(interpolation),
+                                    int(mode), ctypes.byref(cpost) if cpost is not None else None,
+                                    planes["count"].data_ptr() if planes["count"] is not None else None,
+                                    planes["coverage"].data_ptr() if planes["coverage"] is not None else None,
+                                    device, _stream_handle(stream))
+    del keep
+    _check(st)
+    return planes["count"], planes["coverage"]
+
+
+def camera_unproject(camera, uv):
+    """lrp_camera_unproject (host only): the rays of the pixel positions uv (N, 2) of a calibrated camera — the inverse the
+    camera_view() kernel evaluates, with its bits; the library's undistortPoints.  Returns (rays (N, 3) float32, has_ray (N,)
+    bool); a BROWN ray is (X, Y, -1), a FISHEYE ray has unit length."""
+    uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+    n = uv.shape[0]
+    rays = np.empty((n, 3), dtype=np.float32)
+    has_ray = np.empty(n, dtype=np.uint8)
+    c = camera.to_c()
+    _check(_native.load().lrp_camera_unproject(ctypes.byref(c), uv.ctypes.data, n, rays.ctypes.data, has_ray.ctypes.data))
+    return rays, has_ray.astype(bool)
 
 
 def reproject_multi(in_image, out_images, num_samples, interpolation, rotation_matrices=None, post=None, device=None,

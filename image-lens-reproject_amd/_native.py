@@ -131,6 +131,12 @@ SYMBOLS = {
          ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
     ),
     "lrp_camera_limit": (ctypes.c_int, [_P(LrpCamera), _P(ctypes.c_float)]),
+    "lrp_camera_view_device": (
+        ctypes.c_int,
+        [_P(LrpCamera), ctypes.c_int, _FLOATP, _P(LrpCamera), _FLOATP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(LrpPost),
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
+    ),
+    "lrp_camera_unproject": (ctypes.c_int, [_P(LrpCamera), _FLOATP, ctypes.c_int, _FLOATP, ctypes.c_void_p]),
     "lrp_reproject_multi": (
         ctypes.c_int,
         [_P(LrpImage), _P(LrpImage), ctypes.c_int, ctypes.c_int, ctypes.c_int, _FLOATP, _P(LrpPost), _P(ctypes.c_int), ctypes.c_int],

@@ -2,7 +2,7 @@
 // reference's dispatch order, kernel-argument construction, device buffers,
 // streams and the batch context.  Host code only; the kernels live in the
 // lrp_kernels_*.hip / lrp_tile_*.hip / lrp_eqs_*.hip / lrp_stg_*.hip (reprojection), lrp_tables.hip, lrp_geo_lists.hip,
-// lrp_coverage.hip (coverage planes), lrp_compose*.hip (compose), lrp_camera*.hip (compose, calibrated cameras), lrp_packed*.hip (packed pixels), lrp_lanczos*.hip (the Lanczos-3 sampler), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
+// lrp_coverage.hip (coverage planes), lrp_compose*.hip (compose), lrp_camera*.hip (compose, calibrated cameras), lrp_camview*.hip (a calibrated camera as the target), lrp_packed*.hip (packed pixels), lrp_lanczos*.hip (the Lanczos-3 sampler), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,6 +22,8 @@
 
 #include "../../include/lrp.h"
 #include "lrp_camera.h"
+#include "lrp_camera_inverse.h"
+#include "lrp_camview.h"
 #include "lrp_compose.h"
 #include "lrp_compose_packed.h"
 #include "lrp_compose_ss.h"
@@ -53,6 +55,8 @@ __attribute__((weak)) hipError_t launch_compose(const ComposeParams &P, int out_
 __attribute__((weak)) hipError_t launch_compose_ss(const ComposeSsParams &P, int out_lens, int in_mode, int interpolation, hipStream_t stream);
 // lrp_camera.hip, weak like launch_compose (enqueue_compose_cameras).
 __attribute__((weak)) hipError_t launch_compose_cameras(const CameraParams &P, int out_lens, int interpolation, hipStream_t stream);
+// lrp_camview.hip, weak likewise (enqueue_camera_view).
+__attribute__((weak)) hipError_t launch_camera_view(const CameraViewParams &P, int interpolation, hipStream_t stream);
 // lrp_packed.hip, weak like launch_coverage (enqueue_packed).
 __attribute__((weak)) hipError_t launch_packed(PackedParams P, int in_format, int out_lens, int in_mode, int interpolation, int device, hipStream_t stream);
 // lrp_compose_packed.hip, weak like launch_coverage (enqueue_compose_packed).
@@ -719,6 +723,28 @@ int camera_radial(const lrp_camera &cam, double c[4]) {
   return 5;
 }
 
+// The checks of one camera, in the order include/lrp.h states: model, size (with `channels`), data (a source; a target's is
+// ignored), intrinsics, the used coefficients, limit.  `who` starts the lrp_last_error text.
+int validate_camera(const lrp_camera &cam, const std::string &who, int channels, bool needs_data) {
+  if (cam.model != LRP_CAMERA_BROWN && cam.model != LRP_CAMERA_FISHEYE) return fail(LRP_ERR_BAD_ARG, who + "unknown model");
+  if (cam.width < 1 || cam.height < 1) return fail(LRP_ERR_BAD_DIMS, who + "width and height must be positive");
+  if ((unsigned long long)cam.width * (unsigned long long)cam.height * (unsigned long long)channels > kMaxImageFloats)
+    return fail(LRP_ERR_BAD_DIMS, who + "a frame of more than 2^31 floats (8 GiB) cannot be addressed");
+  if (needs_data && !cam.data) return fail(LRP_ERR_NULL, who + "data is null");
+  const float intrinsics[4] = {cam.fx, cam.fy, cam.cx, cam.cy};
+  static const char *const names[4] = {"fx", "fy", "cx", "cy"};
+  for (int j = 0; j < 4; ++j)
+    if (!std::isfinite(intrinsics[j])) return fail(LRP_ERR_BAD_ARG, who + names[j] + " is not finite");
+  double c[4];
+  const int used = camera_radial(cam, c);
+  for (int j = 0; j < used; ++j)
+    if (!std::isfinite(cam.k[j])) return fail(LRP_ERR_BAD_ARG, who + "k[" + std::to_string(j) + "] is not finite");
+  if (cam.fx == 0.0f) return fail(LRP_ERR_BAD_ARG, who + "fx must not be 0");
+  if (cam.fy == 0.0f) return fail(LRP_ERR_BAD_ARG, who + "fy must not be 0");
+  if (!(cam.limit >= 0.0f)) return fail(LRP_ERR_BAD_ARG, who + "limit must be >= 0 (+inf allowed)");
+  return LRP_OK;
+}
+
 // lrp_compose_cameras_device's checks, in the order include/lrp.h states.
 int validate_compose_cameras(const lrp_camera *cams, int n_in, const lrp_image *out, int num_samples, int interpolation, int mode) {
   if (n_in < 1 || n_in > LRP_COMPOSE_MAX_SOURCES)
@@ -733,28 +759,21 @@ int validate_compose_cameras(const lrp_camera *cams, int n_in, const lrp_image *
   if (interpolation != LRP_NEAREST && interpolation != LRP_BILINEAR && interpolation != LRP_BICUBIC)
     return fail(LRP_ERR_INTERPOLATION, "Interpolation method not supported.");
   for (int i = 0; i < n_in; ++i) {
-    const lrp_camera &cam = cams[i];
-    const std::string who = "camera " + std::to_string(i) + ": ";
-    if (cam.model != LRP_CAMERA_BROWN && cam.model != LRP_CAMERA_FISHEYE) return fail(LRP_ERR_BAD_ARG, who + "unknown model");
-    if (cam.width < 1 || cam.height < 1) return fail(LRP_ERR_BAD_DIMS, who + "width and height must be positive");
-    if ((unsigned long long)cam.width * (unsigned long long)cam.height * (unsigned long long)out->channels > kMaxImageFloats)
-      return fail(LRP_ERR_BAD_DIMS, who + "a frame of more than 2^31 floats (8 GiB) cannot be addressed");
-    if (!cam.data) return fail(LRP_ERR_NULL, who + "data is null");
-    const float intrinsics[4] = {cam.fx, cam.fy, cam.cx, cam.cy};
-    static const char *const names[4] = {"fx", "fy", "cx", "cy"};
-    for (int j = 0; j < 4; ++j)
-      if (!std::isfinite(intrinsics[j])) return fail(LRP_ERR_BAD_ARG, who + names[j] + " is not finite");
-    double c[4];
-    const int used = camera_radial(cam, c);
-    for (int j = 0; j < used; ++j)
-      if (!std::isfinite(cam.k[j])) return fail(LRP_ERR_BAD_ARG, who + "k[" + std::to_string(j) + "] is not finite");
-    if (cam.fx == 0.0f) return fail(LRP_ERR_BAD_ARG, who + "fx must not be 0");
-    if (cam.fy == 0.0f) return fail(LRP_ERR_BAD_ARG, who + "fy must not be 0");
-    if (!(cam.limit >= 0.0f)) return fail(LRP_ERR_BAD_ARG, who + "limit must be >= 0 (+inf allowed)");
+    const int st = validate_camera(cams[i], "camera " + std::to_string(i) + ": ", out->channels, true);
+    if (st != LRP_OK) return st;
   }
   if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
     return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
   return LRP_OK;
+}
+
+// What the kernels read of a camera besides its data pointer and its rotation.
+void pack_camera(lrp::CameraSource &S, const lrp_camera &cam) {
+  S.in_w = cam.width, S.in_h = cam.height;
+  S.model = cam.model;
+  S.fx = cam.fx, S.fy = cam.fy, S.cx = cam.cx, S.cy = cam.cy;
+  std::memcpy(S.k, cam.k, sizeof(S.k));
+  S.limit = cam.limit;
 }
 
 // One launch of the camera compose kernel per group of 8 channels (lrp_camera.hip), each of which writes the planes; no table, no
@@ -769,11 +788,7 @@ int enqueue_compose_cameras(const lrp_camera *cams, int n_in, const float *rotat
   if (post) C.exposure = post->exposure, C.reinhard = post->reinhard;
   for (int i = 0; i < n_in; ++i) {
     lrp::CameraSource &S = C.src[i];
-    S.in_w = cams[i].width, S.in_h = cams[i].height;
-    S.model = cams[i].model;
-    S.fx = cams[i].fx, S.fy = cams[i].fy, S.cx = cams[i].cx, S.cy = cams[i].cy;
-    std::memcpy(S.k, cams[i].k, sizeof(S.k));
-    S.limit = cams[i].limit;
+    pack_camera(S, cams[i]);
     S.has_rot = rotations != nullptr;
     if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
   }
@@ -790,6 +805,62 @@ int enqueue_compose_cameras(const lrp_camera *cams, int n_in, const float *rotat
     C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
     const hipError_t e = lrp::launch_compose_cameras(C, out->lens.type, interpolation, stream);
     if (e != hipSuccess) return hip_fail(e, "camera compose kernel launch");
+  }
+  return LRP_OK;
+}
+
+static_assert(lrp::kCameraInverseSteps == LRP_CAMERA_INVERSE_STEPS, "lrp_camera_inverse.h takes the step count of include/lrp.h");
+
+// lrp_camera_view_device's checks, in the order include/lrp.h states.
+int validate_camera_view(const lrp_camera *cams, int n_in, const lrp_camera *target, const float *out_data, int channels, int num_samples,
+                         int interpolation, int mode) {
+  if (n_in < 1 || n_in > LRP_COMPOSE_MAX_SOURCES)
+    return fail(LRP_ERR_BAD_ARG, "n_in of a compose call must be 1 .. " + std::to_string(LRP_COMPOSE_MAX_SOURCES));
+  if (mode != LRP_COMPOSE_FIRST && mode != LRP_COMPOSE_MEAN && mode != LRP_COMPOSE_FEATHER) return fail(LRP_ERR_BAD_ARG, "unknown compose mode");
+  if (!cams || !target || !out_data) return fail(LRP_ERR_NULL, !cams ? "null camera array" : !target ? "null target camera" : "null output data");
+  int st = validate_camera(*target, "target: ", std::max(channels, 1), false); // (channels < 1 is the next check's)
+  if (st != LRP_OK) return st;
+  if (channels < 1) return fail(LRP_ERR_CHANNELS, "channels must be >= 1");
+  if (interpolation != LRP_NEAREST && interpolation != LRP_BILINEAR && interpolation != LRP_BICUBIC)
+    return fail(LRP_ERR_INTERPOLATION, "Interpolation method not supported.");
+  for (int i = 0; i < n_in; ++i) {
+    st = validate_camera(cams[i], "camera " + std::to_string(i) + ": ", channels, true);
+    if (st != LRP_OK) return st;
+  }
+  if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
+    return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
+  return LRP_OK;
+}
+
+// One launch of the camera-view kernel per group of 8 channels (lrp_camview.hip), each of which writes the planes; no table, no
+// geometry-cache entry, no allocation.
+int enqueue_camera_view(const lrp_camera *cams, int n_in, const float *rotations, const lrp_camera *target, float *out_data, int channels,
+                        int num_samples, int interpolation, int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, hipStream_t stream) {
+  if (!lrp::launch_camera_view) return fail(LRP_ERR_HIP, "the camera-view kernels (lrp_camview.hip) are not part of this build");
+  lrp::CameraViewParams C;
+  std::memset(&C, 0, sizeof(C));
+  C.out_w = target->width, C.out_h = target->height, C.channels = channels;
+  pack_camera(C.target, *target);
+  if (post) C.exposure = post->exposure, C.reinhard = post->reinhard;
+  for (int i = 0; i < n_in; ++i) {
+    lrp::CameraSource &S = C.src[i];
+    pack_camera(S, cams[i]);
+    S.has_rot = rotations != nullptr;
+    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
+  }
+  C.n_src = n_in;
+  C.mode = mode;
+  C.num_samples = num_samples;
+  C.count = count;
+  C.coverage = coverage;
+  const int group = lrp::kComposeMaxChannels;
+  for (int c0 = 0; c0 < channels; c0 += group) {
+    for (int i = 0; i < n_in; ++i) C.src[i].data = cams[i].data + c0;
+    C.dst = out_data + c0;
+    C.ch_count = std::min(group, channels - c0);
+    C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
+    const hipError_t e = lrp::launch_camera_view(C, interpolation, stream);
+    if (e != hipSuccess) return hip_fail(e, "camera-view kernel launch");
   }
   return LRP_OK;
 }
@@ -1115,6 +1186,38 @@ int lrp_compose_cameras_device(const lrp_camera *cams, int n_in, const float *ro
   st = select_device(device);
   if (st != LRP_OK) return st;
   return enqueue_compose_cameras(cams, n_in, rotations, out, num_samples, interpolation, mode, post, count, coverage, (hipStream_t)stream);
+}
+
+int lrp_camera_view_device(const lrp_camera *cams, int n_in, const float *rotations, const lrp_camera *target, float *out_data, int channels,
+                           int num_samples, int interpolation, int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, int device,
+                           void *stream) {
+  int st = validate_camera_view(cams, n_in, target, out_data, channels, num_samples, interpolation, mode);
+  if (st != LRP_OK) return st;
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_camera_view(cams, n_in, rotations, target, out_data, channels, num_samples, interpolation, mode, post, count, coverage,
+                             (hipStream_t)stream);
+}
+
+// Host only: camera_unproject (lrp_camera_inverse.h), the function the kernel calls, on the host.
+int lrp_camera_unproject(const lrp_camera *cam, const float *uv, int n, float *rays, uint8_t *has_ray) {
+  if (!cam || !uv || !rays) return fail(LRP_ERR_NULL, "null camera, uv or rays");
+  if (n < 0) return fail(LRP_ERR_BAD_ARG, "n must be >= 0");
+  lrp_camera c = *cam;
+  c.width = c.height = 1; // (the size is not looked at; what is left of the checks is LRP_ERR_BAD_ARG)
+  const int st = validate_camera(c, "camera: ", 1, false);
+  if (st != LRP_OK) return st;
+  lrp::CameraSource T;
+  std::memset(&T, 0, sizeof(T));
+  pack_camera(T, c);
+  for (int j = 0; j < n; ++j) {
+    float *r = rays + 3 * (size_t)j;
+    const float u = uv[2 * (size_t)j], v = uv[2 * (size_t)j + 1];
+    const bool ok = c.model == LRP_CAMERA_FISHEYE ? lrp::camera_unproject<lrp::kCameraFisheye>(T, u, v, r[0], r[1], r[2])
+                                                  : lrp::camera_unproject<lrp::kCameraBrown>(T, u, v, r[0], r[1], r[2]);
+    if (has_ray) has_ray[j] = ok ? 1 : 0;
+  }
+  return LRP_OK;
 }
 
 // Host only, in double.  g(x) = x * (1 + c0 x^2 + c1 x^4 + c2 x^6 + c3 x^8) is scanned upwards in steps of h while it increases; the

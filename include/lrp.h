@@ -439,6 +439,80 @@ int lrp_compose_cameras_device(const lrp_camera *cams, int n_in, const float *ro
                                uint8_t *coverage /* out->width * out->height bytes, or NULL */, int device, void *stream);
 int lrp_camera_limit(const lrp_camera *cam, float *limit);
 
+/* ---- calibrated camera as the target: a new camera matrix, camera to camera, re-distortion ---- */
+
+/* lrp_compose_cameras_device whose OUTPUT is the frame of a calibrated camera too: an undistorted or rectified view with its
+ * own fx, fy, cx, cy (OpenCV's newCameraMatrix), the frame of camera A as camera B would have recorded it (Kannala-Brandt to
+ * Brown-Conrady and back), a rendering with the distortion of a real lens.  The polynomials are closed-form from ray to pixel;
+ * the target needs the other direction, pixel to ray, and gets it from a fixed number of Newton steps.
+ *
+ * Definition.  Everything is the definition of lrp_compose_cameras_device — the sources, rotations, coverage per sub-sample,
+ * FIRST / MEAN / FEATHER, m, 1.0f / (float)m, post, both planes, one launch per group of 8 channels — with the target ray
+ * replaced.  The target is an lrp_camera T: T.data is ignored, T.width and T.height are the output size.  For output pixel
+ * x, y and sub-sample ssx, ssy (the order of lrp_compose_ss_device), n = num_samples, ns1 = (float)n + 1.0f; binary32,
+ * un-fused, in the order written; k1 .. are T.k[]:
+ *   u  = ((float)x + ((float)ssx + 1.0f) / ns1) - 0.5f;   v likewise from y, ssy          (n == 1: u == x exactly)
+ *   x0 = (u - T.cx) / T.fx;   y0 = (v - T.cy) / T.fy;
+ *   LRP_CAMERA_BROWN
+ *     X = x0;  Y = y0;  ok = (X*X + Y*Y <= T.limit);
+ *     repeat LRP_CAMERA_INVERSE_STEPS times:
+ *       r2 = X*X + Y*Y;  ab = X*Y;
+ *       L  = 1.0f + r2*(k1 + r2*(k2 + r2*k3));          D = k1 + r2*((2.0f*k2) + r2*(3.0f*k3));
+ *       xd = X*L + ((2.0f*p1)*ab + p2*(r2 + 2.0f*(X*X)));   yd = Y*L + (p1*(r2 + 2.0f*(Y*Y)) + (2.0f*p2)*ab);
+ *       ex = xd - x0;  ey = yd - y0;
+ *       jxx = ((L + (2.0f*(X*X))*D) + (2.0f*p1)*Y) + (6.0f*p2)*X;
+ *       jxy = (((2.0f*ab)*D) + (2.0f*p1)*X) + (2.0f*p2)*Y;
+ *       jyy = ((L + (2.0f*(Y*Y))*D) + (6.0f*p1)*Y) + (2.0f*p2)*X;
+ *       det = jxx*jyy - jxy*jxy;
+ *       Xn = X - (jyy*ex - jxy*ey)/det;   Yn = Y - (jxx*ey - jxy*ex)/det;   X = Xn;  Y = Yn;
+ *       ok = ok && (X*X + Y*Y <= T.limit);                    (a comparison with NaN is false, and ok stays false)
+ *     once more r2, ab, L, xd, yd, ex, ey at the final X, Y;
+ *     has_ray = ok && fabsf(T.fx*ex) <= 0.5f && fabsf(T.fy*ey) <= 0.5f;          ray = (X, Y, -1.0f)
+ *   LRP_CAMERA_FISHEYE
+ *     rd = sqrtf(x0*x0 + y0*y0);  th = rd;  ok = (th <= T.limit);
+ *     repeat LRP_CAMERA_INVERSE_STEPS times:
+ *       t2 = th*th;
+ *       g  = th*(1.0f + t2*(k1 + t2*(k2 + t2*(k3 + t2*k4))));
+ *       gp = 1.0f + t2*((3.0f*k1) + t2*((5.0f*k2) + t2*((7.0f*k3) + t2*(9.0f*k4))));
+ *       th = th - (g - rd)/gp;     ok = ok && th >= 0.0f && th <= T.limit;
+ *     once more t2, g at the final th;  e = g - rd;
+ *     has_ray = ok && fabsf(T.fx*e) <= 0.5f && fabsf(T.fy*e) <= 0.5f;
+ *     sincosf(th) -> s, c;  q = (rd > 0.0f) ? s/rd : 0.0f;                       ray = (q*x0, q*y0, -c)
+ * A sub-sample without a ray is covered by no camera: it adds nothing and is counted neither in m nor in count nor in coverage.
+ * A target frame that reaches beyond the point where its own polynomial turns has pixels without a ray; they are +0.0f with
+ * coverage 0, not ghosts.  The BROWN ray is not normalised: both source mappings are invariant to the length of the ray.  ok is
+ * sticky because an iterate that has left the region where the polynomial is monotonic may wander back in by accident.  Newton
+ * with the full 2 x 2 Jacobian, not OpenCV's fixed-point iteration, which converges linearly, and near the turning point not at
+ * all.  The residual test (half a pixel) rejects what 8 steps did not bring home.
+ *
+ * lrp_camera_view_device: asynchronous on `stream`; allocates nothing, does not synchronise, builds no table, neither reads nor
+ * writes the geometry cache.  out_data: target->width * target->height * channels floats on the device; every camera has
+ * `channels` channels.  count, coverage: target->width * target->height bytes each, or NULL.  Errors, all before a device is
+ * touched, in this order:
+ *   1. n_in outside 1 .. LRP_COMPOSE_MAX_SOURCES or an unknown mode: LRP_ERR_BAD_ARG;
+ *   2. cams, target or out_data NULL: LRP_ERR_NULL;
+ *   3. the target: an unknown model: LRP_ERR_BAD_ARG; a non-positive size or more than 2^31 floats (width * height * channels):
+ *      LRP_ERR_BAD_DIMS; fx, fy, cx, cy or a used k not finite, fx or fy equal to 0, or limit NaN or negative: LRP_ERR_BAD_ARG
+ *      with an lrp_last_error text that begins "target: ".  limit need not be finite: with +inf, ok rests on NaN alone;
+ *   4. channels < 1: LRP_ERR_CHANNELS;
+ *   5. interpolation outside 0 .. 2: LRP_ERR_INTERPOLATION;
+ *   6. per camera, ascending: the checks of lrp_compose_cameras_device;
+ *   7. num_samples outside 1 .. 15: LRP_ERR_BAD_ARG.
+ *
+ * lrp_camera_unproject (host only): the definition from x0, y0 on, for n given positions u, v in pixels: rays[3 * j ..] and
+ * has_ray[j] (or NULL), the bits of the device.  It is the library's undistortPoints.  cam->data, width and height are not
+ * looked at.  Errors: cam, uv or rays NULL: LRP_ERR_NULL; n < 0, an unknown model, or fx, fy, cx, cy, a used k or limit that
+ * the target checks above refuse: LRP_ERR_BAD_ARG.
+ *
+ * An ideal pinhole or equidistant SOURCE is expressible as a camera with k = 0; an equirectangular one is not. */
+#define LRP_CAMERA_INVERSE_STEPS 8
+int lrp_camera_view_device(const lrp_camera *cams, int n_in, const float *rotations /* n_in x 9, or NULL */,
+                           const lrp_camera *target, float *out_data, int channels, int num_samples, int interpolation,
+                           int mode, const lrp_post *post, uint8_t *count /* target->width * target->height bytes, or NULL */,
+                           uint8_t *coverage /* target->width * target->height bytes, or NULL */, int device, void *stream);
+int lrp_camera_unproject(const lrp_camera *cam, const float *uv /* n x 2, pixels */, int n, float *rays /* n x 3 */,
+                         uint8_t *has_ray /* n, or NULL */);
+
 /* ---- one source, several outputs, several GPUs (BASELINE configs[4]) ---------- */
 
 /* One host source, n_out host outputs (lenses in outs[i].lens, rotations + 9 * i or none): the
