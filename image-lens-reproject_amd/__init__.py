@@ -23,7 +23,11 @@ frames of calibrated cameras (Camera: fx, fy, cx, cy and Brown-Conrady or
 Kannala-Brandt distortion coefficients) instead of ideal lenses, and
 camera_view(cameras, target, out, num_samples, interpolation, ...) renders them
 into the frame of another calibrated camera (camera_unproject(camera, uv) is
-the pixel-to-ray inverse it uses, on the host).
+the pixel-to-ray inverse it uses, on the host), and
+camera_overlap(cameras, out_image, ...) -> camera_gains(stats, n) ->
+compose_cameras(..., gains=g) match the cameras' exposures: the statistic of the
+pairwise overlaps by one launch, gain compensation on the host, and compose with
+one gain per camera.
 
 The directory name contains a hyphen (it is the name the build contract fixes);
 import it with importlib.import_module("image-lens-reproject_amd").
@@ -495,10 +499,12 @@ def camera_limit(camera):
 
 
 def compose_cameras(cameras, out_image, num_samples, interpolation, rotation_matrices=None, mode=ComposeMode.FIRST, post=None,
-                    count=None, coverage=None, device=None, stream=None):
+                    count=None, coverage=None, device=None, stream=None, gains=None):
     """lrp_compose_cameras_device (include/lrp.h "compose, calibrated cameras"): compose_ss() whose sources are frames of
     calibrated cameras (Camera; the models may be mixed), by one launch; a single camera into a rectilinear out_image
-    undistorts it.  Device tensors only; asynchronous on `stream`.  count / coverage and the return value: as compose_ss()."""
+    undistorts it.  Device tensors only; asynchronous on `stream`.  count / coverage and the return value: as compose_ss().
+    gains: one factor per camera on its first min(channels, 3) channels (camera_gains()); anything but None takes
+    lrp_compose_cameras_gain_device (include/lrp.h "exposure matching across a camera rig")."""
     lib = _native.load()
     n = len(cameras)
     wanted = {}
@@ -528,14 +534,62 @@ def compose_cameras(cameras, out_image, num_samples, interpolation, rotation_mat
         keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
         rot = keep.ctypes.data
     cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
-    st = lib.lrp_compose_cameras_device(arr, n, rot, ctypes.byref(cout), int(num_samples), int(interpolation), int(mode),
-                                        ctypes.byref(cpost) if cpost is not None else None,
-                                        planes["count"].data_ptr() if planes["count"] is not None else None,
-                                        planes["coverage"].data_ptr() if planes["coverage"] is not None else None,
-                                        device, _stream_handle(stream))
+    tail = (ctypes.byref(cout), int(num_samples), int(interpolation), int(mode), ctypes.byref(cpost) if cpost is not None else None,
+            planes["count"].data_ptr() if planes["count"] is not None else None,
+            planes["coverage"].data_ptr() if planes["coverage"] is not None else None, device, _stream_handle(stream))
+    if gains is None:
+        st = lib.lrp_compose_cameras_device(arr, n, rot, *tail)
+    else:
+        g = np.ascontiguousarray(np.asarray(gains.cpu() if _is_torch(gains) else gains, dtype=np.float32).reshape(-1))
+        if g.size != n:
+            raise ValueError("gains must hold one value per camera")
+        st = lib.lrp_compose_cameras_gain_device(arr, n, rot, g.ctypes.data, *tail)
     del keep
     _check(st)
     return planes["count"], planes["coverage"]
+
+
+def camera_overlap(cameras, out_image, rotation_matrices=None, lo=0.02, hi=0.98, stats=None, device=None, stream=None):
+    """lrp_camera_overlap_device (include/lrp.h "exposure matching across a camera rig"): the statistic of the cameras' pairwise
+    overlaps in out_image's geometry (its lens, size and channel count; its data is not looked at), by one launch: an int64 CUDA
+    tensor of shape (8, 8, 2) with [i, j] = (N_ij, S_ij) — the number of output pixels at which cameras i and j both have a
+    luminance inside [lo, hi], and the sum of camera i's luminance over them in units of 1 / 65536.  stats: a tensor to write
+    into (every word is overwritten), or None to allocate one.  Asynchronous on `stream`."""
+    import torch
+
+    lib = _native.load()
+    n = len(cameras)
+    if not all(c.on_device() for c in cameras):
+        raise ValueError("camera_overlap() takes device tensors only: the data of every camera must be a CUDA tensor")
+    if device is None:
+        device = cameras[0].data.device.index if n else 0
+    if stats is None:
+        stats = torch.empty((8, 8, 2), dtype=torch.int64, device=f"cuda:{device}")
+    elif not _is_torch(stats) or stats.dtype != torch.int64 or not stats.is_cuda or not stats.is_contiguous() or stats.numel() != 128:
+        raise ValueError("stats must be a contiguous int64 CUDA tensor with 8*8*2 elements")
+    arr = (_native.LrpCamera * max(n, 1))(*[c.to_c(out_image.channels) for c in cameras])
+    cout = Image(out_image.lens, out_image.width, out_image.height, out_image.channels, None).to_c()
+    rot, keep = None, None
+    if rotation_matrices is not None:
+        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
+        rot = keep.ctypes.data
+    st = lib.lrp_camera_overlap_device(arr, n, rot, ctypes.byref(cout), float(lo), float(hi), stats.data_ptr(), device, _stream_handle(stream))
+    del keep
+    _check(st)
+    return stats
+
+
+def camera_gains(stats, n, sigma_n=10 / 255, sigma_g=0.1):
+    """lrp_camera_gains (host only): Brown and Lowe's gain compensation on the table of camera_overlap() — a tensor or an array
+    of 8 * 8 * 2 integers, copied to the host — for its first n cameras: float32[n], the factor per camera that equalises the
+    overlaps' mean luminances under a prior of unit gain.  A camera without a valid pixel gets 1.0."""
+    host = stats.cpu().numpy() if _is_torch(stats) else np.asarray(stats)
+    table = np.ascontiguousarray(host.astype(np.uint64, copy=False).reshape(-1))
+    if table.size != 128:
+        raise ValueError("stats must hold 8*8*2 integers")
+    gains = np.empty(max(int(n), 1), dtype=np.float32)
+    _check(_native.load().lrp_camera_gains(table.ctypes.data, int(n), float(sigma_n), float(sigma_g), gains.ctypes.data))
+    return gains[: int(n)]
 
 
 def camera_view(cameras, target, out, num_samples, interpolation, rotation_matrices=None, mode=ComposeMode.FIRST, post=None, count=None,

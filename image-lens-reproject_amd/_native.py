@@ -137,6 +137,16 @@ SYMBOLS = {
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
     ),
     "lrp_camera_unproject": (ctypes.c_int, [_P(LrpCamera), _FLOATP, ctypes.c_int, _FLOATP, ctypes.c_void_p]),
+    "lrp_camera_overlap_device": (
+        ctypes.c_int,
+        [_P(LrpCamera), ctypes.c_int, _FLOATP, _P(LrpImage), ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
+    ),
+    "lrp_camera_gains": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, _FLOATP]),
+    "lrp_compose_cameras_gain_device": (
+        ctypes.c_int,
+        [_P(LrpCamera), ctypes.c_int, _FLOATP, _FLOATP, _P(LrpImage), ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(LrpPost), ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
+    ),
     "lrp_reproject_multi": (
         ctypes.c_int,
         [_P(LrpImage), _P(LrpImage), ctypes.c_int, ctypes.c_int, ctypes.c_int, _FLOATP, _P(LrpPost), _P(ctypes.c_int), ctypes.c_int],

@@ -23,6 +23,8 @@
 #include "../../include/lrp.h"
 #include "lrp_camera.h"
 #include "lrp_camera_inverse.h"
+#include "lrp_camgain.h"
+#include "lrp_camstat.h"
 #include "lrp_camview.h"
 #include "lrp_compose.h"
 #include "lrp_compose_packed.h"
@@ -57,6 +59,9 @@ __attribute__((weak)) hipError_t launch_compose_ss(const ComposeSsParams &P, int
 __attribute__((weak)) hipError_t launch_compose_cameras(const CameraParams &P, int out_lens, int interpolation, hipStream_t stream);
 // lrp_camview.hip, weak likewise (enqueue_camera_view).
 __attribute__((weak)) hipError_t launch_camera_view(const CameraViewParams &P, int interpolation, hipStream_t stream);
+// lrp_camstat.hip and lrp_camgain.hip, weak likewise (enqueue_camera_overlap, enqueue_compose_cameras_gain).
+__attribute__((weak)) hipError_t launch_camera_overlap(const CameraStatParams &P, int out_lens, hipStream_t stream);
+__attribute__((weak)) hipError_t launch_compose_cameras_gain(const CameraGainParams &G, int out_lens, int interpolation, hipStream_t stream);
 // lrp_packed.hip, weak like launch_coverage (enqueue_packed).
 __attribute__((weak)) hipError_t launch_packed(PackedParams P, int in_format, int out_lens, int in_mode, int interpolation, int device, hipStream_t stream);
 // lrp_compose_packed.hip, weak like launch_coverage (enqueue_compose_packed).
@@ -745,23 +750,34 @@ int validate_camera(const lrp_camera &cam, const std::string &who, int channels,
   return LRP_OK;
 }
 
-// lrp_compose_cameras_device's checks, in the order include/lrp.h states.
-int validate_compose_cameras(const lrp_camera *cams, int n_in, const lrp_image *out, int num_samples, int interpolation, int mode) {
+// Items 1 to 5 of lrp_compose_cameras_device's checks, in the order include/lrp.h states.  gains: checked for NULL with item 2
+// when wants_gains (lrp_compose_cameras_gain_device); needs_out_data: false for a call that writes no image
+// (lrp_camera_overlap_device).
+int validate_cameras_and_output(const lrp_camera *cams, int n_in, const lrp_image *out, int interpolation, int mode, bool needs_out_data,
+                                bool wants_gains, const float *gains) {
   if (n_in < 1 || n_in > LRP_COMPOSE_MAX_SOURCES)
     return fail(LRP_ERR_BAD_ARG, "n_in of a compose call must be 1 .. " + std::to_string(LRP_COMPOSE_MAX_SOURCES));
   if (mode != LRP_COMPOSE_FIRST && mode != LRP_COMPOSE_MEAN && mode != LRP_COMPOSE_FEATHER) return fail(LRP_ERR_BAD_ARG, "unknown compose mode");
   if (!cams || !out) return fail(LRP_ERR_NULL, cams ? "null image" : "null camera array");
+  if (wants_gains && !gains) return fail(LRP_ERR_NULL, "null gains");
   if (!lens_in_hot_path(out->lens.type, g_lens_ext.load(std::memory_order_relaxed))) return fail(LRP_ERR_OUTPUT_LENS, "Output lens type not supported.");
   if (out->channels < 1) return fail(LRP_ERR_CHANNELS, "out->channels must be >= 1");
   if (out->width < 1 || out->height < 1) return fail(LRP_ERR_BAD_DIMS, "image dimensions must be positive");
   if (!image_addressable(*out)) return fail(LRP_ERR_BAD_DIMS, "an image of more than 2^31 floats (8 GiB) cannot be addressed");
-  if (!out->data) return fail(LRP_ERR_NULL, "null image data");
+  if (needs_out_data && !out->data) return fail(LRP_ERR_NULL, "null image data");
   if (interpolation != LRP_NEAREST && interpolation != LRP_BILINEAR && interpolation != LRP_BICUBIC)
     return fail(LRP_ERR_INTERPOLATION, "Interpolation method not supported.");
   for (int i = 0; i < n_in; ++i) {
     const int st = validate_camera(cams[i], "camera " + std::to_string(i) + ": ", out->channels, true);
     if (st != LRP_OK) return st;
   }
+  return LRP_OK;
+}
+
+// lrp_compose_cameras_device's checks, in the order include/lrp.h states.
+int validate_compose_cameras(const lrp_camera *cams, int n_in, const lrp_image *out, int num_samples, int interpolation, int mode) {
+  const int st = validate_cameras_and_output(cams, n_in, out, interpolation, mode, true, false, nullptr);
+  if (st != LRP_OK) return st;
   if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
     return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
   return LRP_OK;
@@ -805,6 +821,71 @@ int enqueue_compose_cameras(const lrp_camera *cams, int n_in, const float *rotat
     C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
     const hipError_t e = lrp::launch_compose_cameras(C, out->lens.type, interpolation, stream);
     if (e != hipSuccess) return hip_fail(e, "camera compose kernel launch");
+  }
+  return LRP_OK;
+}
+
+static_assert(lrp::kOverlapWords == LRP_OVERLAP_WORDS, "lrp_camstat.h states the table size of include/lrp.h");
+
+// The launcher (lrp_camstat.hip) zeroes the table on `stream` ahead of the one launch of the overlap kernel, which adds into it; no
+// allocation, no synchronisation, no geometry-cache entry.
+int enqueue_camera_overlap(const lrp_camera *cams, int n_in, const float *rotations, const lrp_image *out, float lo, float hi, uint64_t *stats,
+                           hipStream_t stream) {
+  if (!lrp::launch_camera_overlap) return fail(LRP_ERR_HIP, "the camera overlap kernels (lrp_camstat.hip) are not part of this build");
+  lrp::CameraStatParams C;
+  std::memset(&C, 0, sizeof(C));
+  C.stats = reinterpret_cast<unsigned long long *>(stats);
+  C.out_w = out->width, C.out_h = out->height, C.channels = out->channels;
+  C.ch_count = std::min(out->channels, 3);
+  C.out_lens = pack_lens(out->lens);
+  C.n_src = n_in;
+  C.lo = lo, C.hi = hi;
+  for (int i = 0; i < n_in; ++i) {
+    lrp::CameraSource &S = C.src[i];
+    pack_camera(S, cams[i]);
+    S.data = cams[i].data;
+    S.has_rot = rotations != nullptr;
+    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
+  }
+  const hipError_t e = lrp::launch_camera_overlap(C, out->lens.type, stream);
+  if (e != hipSuccess) return hip_fail(e, "zeroing the overlap table or the camera overlap kernel launch");
+  return LRP_OK;
+}
+
+// enqueue_compose_cameras with gains: the first group of 8 channels — the one that holds the colour channels — goes through the
+// gain kernel (lrp_camgain.hip), the further groups, which the gains do not touch, through the camera compose kernel itself.
+int enqueue_compose_cameras_gain(const lrp_camera *cams, int n_in, const float *rotations, const float *gains, const lrp_image *out,
+                                 int num_samples, int interpolation, int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage,
+                                 hipStream_t stream) {
+  if (!lrp::launch_compose_cameras_gain) return fail(LRP_ERR_HIP, "the camera gain compose kernels (lrp_camgain.hip) are not part of this build");
+  if (!lrp::launch_compose_cameras) return fail(LRP_ERR_HIP, "the camera compose kernels (lrp_camera.hip) are not part of this build");
+  lrp::CameraGainParams G;
+  std::memset(&G, 0, sizeof(G));
+  lrp::CameraParams &C = G.cam;
+  C.out_w = out->width, C.out_h = out->height, C.channels = out->channels;
+  C.out_lens = pack_lens(out->lens);
+  if (post) C.exposure = post->exposure, C.reinhard = post->reinhard;
+  for (int i = 0; i < n_in; ++i) {
+    lrp::CameraSource &S = C.src[i];
+    pack_camera(S, cams[i]);
+    S.has_rot = rotations != nullptr;
+    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
+    G.gain[i] = gains[i];
+  }
+  C.n_src = n_in;
+  C.mode = mode;
+  C.num_samples = num_samples;
+  C.count = count;
+  C.coverage = coverage;
+  const int channels = out->channels, group = lrp::kComposeMaxChannels;
+  for (int c0 = 0; c0 < channels; c0 += group) {
+    for (int i = 0; i < n_in; ++i) C.src[i].data = cams[i].data + c0;
+    C.dst = out->data + c0;
+    C.ch_count = std::min(group, channels - c0);
+    C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
+    const hipError_t e = c0 == 0 ? lrp::launch_compose_cameras_gain(G, out->lens.type, interpolation, stream)
+                                 : lrp::launch_compose_cameras(C, out->lens.type, interpolation, stream);
+    if (e != hipSuccess) return hip_fail(e, "camera gain compose kernel launch");
   }
   return LRP_OK;
 }
@@ -1186,6 +1267,91 @@ int lrp_compose_cameras_device(const lrp_camera *cams, int n_in, const float *ro
   st = select_device(device);
   if (st != LRP_OK) return st;
   return enqueue_compose_cameras(cams, n_in, rotations, out, num_samples, interpolation, mode, post, count, coverage, (hipStream_t)stream);
+}
+
+int lrp_camera_overlap_device(const lrp_camera *cams, int n_in, const float *rotations, const lrp_image *out, float lo, float hi,
+                              uint64_t *stats, int device, void *stream) {
+  // (no mode and a fixed sampler: items 1 and 4 see values that pass)
+  int st = validate_cameras_and_output(cams, n_in, out, LRP_BILINEAR, LRP_COMPOSE_FIRST, false, false, nullptr);
+  if (st != LRP_OK) return st;
+  if (!stats) return fail(LRP_ERR_NULL, "null stats");
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !(0.0f <= lo && lo <= hi && hi <= 32768.0f))
+    return fail(LRP_ERR_BAD_ARG, "lo and hi of an overlap call must be finite with 0 <= lo <= hi <= 32768");
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_camera_overlap(cams, n_in, rotations, out, lo, hi, stats, (hipStream_t)stream);
+}
+
+// Host only, in double: the normal equations of Brown and Lowe's gain compensation over the cameras with N_kk > 0, solved by
+// Gaussian elimination with partial pivoting.
+int lrp_camera_gains(const uint64_t *stats, int n_in, float sigma_n, float sigma_g, float *gains) {
+  if (!stats || !gains) return fail(LRP_ERR_NULL, "null stats or gains");
+  if (n_in < 1 || n_in > LRP_COMPOSE_MAX_SOURCES) return fail(LRP_ERR_BAD_ARG, "n_in must be 1 .. " + std::to_string(LRP_COMPOSE_MAX_SOURCES));
+  if (!std::isfinite(sigma_n) || !(sigma_n > 0.0f) || !std::isfinite(sigma_g) || !(sigma_g > 0.0f))
+    return fail(LRP_ERR_BAD_ARG, "sigma_n and sigma_g must be finite and positive");
+  constexpr int M = LRP_COMPOSE_MAX_SOURCES;
+  const auto N = [&](int i, int j) { return (double)stats[(i * M + j) * 2]; };
+  const auto I = [&](int i, int j) {
+    const uint64_t n = stats[(i * M + j) * 2];
+    return n == 0 ? 0.0 : (double)stats[(i * M + j) * 2 + 1] / (65536.0 * (double)n);
+  };
+  int active[M], m = 0;
+  for (int k = 0; k < n_in; ++k) {
+    gains[k] = 1.0f;
+    if (stats[(k * M + k) * 2] > 0) active[m++] = k;
+  }
+  if (m == 0) return LRP_OK;
+  const double inv_n2 = 1.0 / ((double)sigma_n * (double)sigma_n), inv_g2 = 1.0 / ((double)sigma_g * (double)sigma_g);
+  double A[M][M + 1]; // the augmented matrix [A | b]
+  for (int r = 0; r < m; ++r) {
+    const int k = active[r];
+    double diag = 0.0, prior = 0.0;
+    for (int c = 0; c < m; ++c) {
+      const int j = active[c];
+      prior += N(k, j) * inv_g2;
+      if (j == k) continue;
+      diag += 2.0 * N(k, j) * I(k, j) * I(k, j) * inv_n2;
+      A[r][c] = -2.0 * N(k, j) * I(k, j) * I(j, k) * inv_n2;
+    }
+    A[r][r] = diag + prior;
+    A[r][m] = prior;
+  }
+  for (int p = 0; p < m; ++p) { // elimination with partial pivoting
+    int best = p;
+    for (int r = p + 1; r < m; ++r)
+      if (std::fabs(A[r][p]) > std::fabs(A[best][p])) best = r;
+    if (A[best][p] == 0.0) return fail(LRP_ERR_BAD_ARG, "the gain system is singular");
+    if (best != p)
+      for (int c = 0; c <= m; ++c) std::swap(A[p][c], A[best][c]);
+    for (int r = p + 1; r < m; ++r) {
+      const double f = A[r][p] / A[p][p];
+      for (int c = p; c <= m; ++c) A[r][c] -= f * A[p][c];
+    }
+  }
+  double g[M];
+  for (int r = m - 1; r >= 0; --r) {
+    double s = A[r][m];
+    for (int c = r + 1; c < m; ++c) s -= A[r][c] * g[c];
+    g[r] = s / A[r][r];
+  }
+  for (int r = 0; r < m; ++r) gains[active[r]] = (float)g[r];
+  return LRP_OK;
+}
+
+int lrp_compose_cameras_gain_device(const lrp_camera *cams, int n_in, const float *rotations, const float *gains, const lrp_image *out,
+                                    int num_samples, int interpolation, int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage,
+                                    int device, void *stream) {
+  int st = validate_cameras_and_output(cams, n_in, out, interpolation, mode, true, true, gains);
+  if (st != LRP_OK) return st;
+  for (int i = 0; i < n_in; ++i)
+    if (!std::isfinite(gains[i]) || gains[i] < 0.0f)
+      return fail(LRP_ERR_BAD_ARG, "camera " + std::to_string(i) + ": gain must be finite and not negative");
+  if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
+    return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_compose_cameras_gain(cams, n_in, rotations, gains, out, num_samples, interpolation, mode, post, count, coverage,
+                                      (hipStream_t)stream);
 }
 
 int lrp_camera_view_device(const lrp_camera *cams, int n_in, const float *rotations, const lrp_camera *target, float *out_data, int channels,

@@ -513,6 +513,60 @@ int lrp_camera_view_device(const lrp_camera *cams, int n_in, const float *rotati
 int lrp_camera_unproject(const lrp_camera *cam, const float *uv /* n x 2, pixels */, int n, float *rays /* n x 3 */,
                          uint8_t *has_ray /* n, or NULL */);
 
+/* ---- exposure matching across a camera rig: overlap statistics, gains, compose with gains ---- */
+
+/* Cameras on auto-exposure differ by a third of a stop or more; FIRST then shows a step at every seam, MEAN and FEATHER a band.
+ * Three calls measure and remove it: the statistic of the pairwise overlaps in one launch, Brown and Lowe's gain compensation
+ * on the host, and lrp_compose_cameras_device with one gain per camera.
+ *
+ * lrp_camera_overlap_device.  Definition, binary32, un-fused, in the order written.  For each output pixel take the single
+ * sub-sample of num_samples == 1 (the pixel centre).  The target ray, rotation i, sx, sy, imaged and covered_i are exactly those
+ * of lrp_compose_cameras_device.  C = out->channels (the frames' stride).  s_i is the BILINEAR sample of the first min(C, 3)
+ * channels of camera i at (sx, sy); the sampler is fixed.
+ *   Y_i     = s_i[0]                                                  when C < 3, otherwise
+ *   Y_i     = (0.25f * s_i[0] + 0.5f * s_i[1]) + 0.25f * s_i[2];
+ *   valid_i = covered_i && Y_i >= lo && Y_i <= hi                     (comparisons with NaN are false)
+ *   q_i     = (uint32_t)(Y_i * 65536.0f)                              (0 <= lo <= hi <= 32768: exact, at most 2^31)
+ * For all i, j < n_in, the diagonal included:
+ *   stats[(i * 8 + j) * 2]     = N_ij, the number of pixels with valid_i && valid_j;
+ *   stats[(i * 8 + j) * 2 + 1] = S_ij, the sum of q_i over those pixels.
+ * Every other word is 0: the call overwrites all LRP_OVERLAP_WORDS words, whatever they held.  The zeroing runs on `stream` ahead
+ * of the kernel; the host does not synchronise.  The sums are integers — the result does not depend on the order of addition and
+ * is exact; with out->width * out->height <= 2^31, S_ij < 2^63.  lo, hi exclude clipped and near-black pixels.
+ * Asynchronous on `stream`; allocates nothing, builds no table, neither reads nor writes the geometry cache.  out: lens and size
+ * only; out->data is not looked at and may be NULL.  Errors, all before a device is touched: those of
+ * lrp_compose_cameras_device, items 1 to 5, in their order, out->data exempt from the NULL check (the interpolation is fixed:
+ * item 4 cannot occur); then stats NULL: LRP_ERR_NULL; then lo or hi not finite, or not 0 <= lo <= hi <= 32768: LRP_ERR_BAD_ARG.
+ *
+ * lrp_camera_gains (host only, double, pure).  Brown and Lowe's gain compensation, as in OpenCV's GainCompensator.  stats is a
+ * HOST copy of the table.  With I_ij = S_ij / (65536.0 * N_ij), taken as 0 where N_ij == 0, it minimises
+ *   e = 1/2 * sum_i sum_j N_ij * ((g_i I_ij - g_j I_ji)^2 / sigma_n^2 + (1 - g_i)^2 / sigma_g^2).
+ * The active set is the cameras with N_kk > 0; a camera with N_kk == 0 gets gain 1.0f and leaves the system.  For the active set
+ *   A[k][k] = sum_{j != k} 2 N_kj I_kj^2 / sigma_n^2 + sum_j N_kj / sigma_g^2        (the second sum includes j == k)
+ *   A[k][j] = -2 N_kj I_kj I_jk / sigma_n^2
+ *   b[k]    = sum_j N_kj / sigma_g^2
+ * and A g = b is solved in double by Gaussian elimination with partial pivoting; gains[k] = (float)g_k.  The table is symmetric
+ * in N by construction, and the function relies on that.  sigma_n is in units of Y; OpenCV's values are 10 / 255 and 0.1.
+ * Errors: stats or gains NULL: LRP_ERR_NULL; n_in outside 1 .. 8: LRP_ERR_BAD_ARG; a sigma that is not finite or not positive:
+ * LRP_ERR_BAD_ARG.
+ *
+ * lrp_compose_cameras_gain_device.  The definition of lrp_compose_cameras_device with one insertion: right after sampling,
+ * s_i[c] = g_i * s_i[c] for the absolute channels c < min(C, 3), g_i = gains[i] — one multiplication per channel, before the
+ * FIRST / MEAN / FEATHER arithmetic, so that FEATHER forms w_i * (g_i * s_i[c]).  Alpha, depth and every further channel are
+ * untouched (with more than 8 channels only the first group's launch multiplies).  Coverage, both planes and post are unchanged.
+ * gains is a HOST array of n_in floats.  Errors: those of lrp_compose_cameras_device in their order; gains NULL: LRP_ERR_NULL,
+ * checked with item 2; a gain that is not finite or is negative: LRP_ERR_BAD_ARG with an lrp_last_error text that names the
+ * camera ("camera 2: gain ..."), checked after item 5. */
+#define LRP_OVERLAP_WORDS 128 /* 8 x 8 x 2 uint64_t, whatever n_in is */
+int lrp_camera_overlap_device(const lrp_camera *cams, int n_in, const float *rotations /* n_in x 9, or NULL */,
+                              const lrp_image *out /* lens and size only; data is not looked at, may be NULL */, float lo, float hi,
+                              uint64_t *stats /* DEVICE, LRP_OVERLAP_WORDS words */, int device, void *stream);
+int lrp_camera_gains(const uint64_t *stats /* HOST copy */, int n_in, float sigma_n, float sigma_g, float *gains /* n_in */);
+int lrp_compose_cameras_gain_device(const lrp_camera *cams, int n_in, const float *rotations /* n_in x 9, or NULL */,
+                                    const float *gains /* HOST, n_in */, const lrp_image *out, int num_samples, int interpolation,
+                                    int mode, const lrp_post *post, uint8_t *count /* out->width * out->height bytes, or NULL */,
+                                    uint8_t *coverage /* out->width * out->height bytes, or NULL */, int device, void *stream);
+
 /* ---- one source, several outputs, several GPUs (BASELINE configs[4]) ---------- */
 
 /* One host source, n_out host outputs (lenses in outs[i].lens, rotations + 9 * i or none): the
