@@ -5,7 +5,10 @@
 // Per output pixel: the target ray once; then, source by source, the rotation, ray_to_source and the coverage test of
 // include/lrp.h "coverage" (what lrp_coverage.hip decides per sub-sample), a sample<> of the sources that cover the pixel, and
 // one store.  No lens formula and no sampler is restated: target_ray, ray_to_source and sample<> are lrp_device.h's, the
-// values — and the bits — those of the one-pixel-per-lane kernel (lrp_kernel_impl.h) for that source.
+// values — and the bits — those of the one-pixel-per-lane kernel (lrp_kernel_impl.h) for that source.  The per-pixel body
+// itself is written twice: here, and in compose_packed_kernel (lrp_compose_packed_kernel.h) between other ends; folded onto
+// one function, kernels of both moved registers.  The supersampled kernels share one body,
+// lrp_compose_pixel.h, and take from here the tile, compose_min, LensSources and launch_compose_tiles.
 //
 // Mapping (gfx950): the 32 x 8 tile of lrp_kernel_impl.h, one pixel per lane, tiles in xcd_tile() order — this kernel reads
 // sources, and neighbouring tiles share source rows in one XCD's L2.  The source loop is wave-uniform: its counter and the
@@ -40,6 +43,18 @@ template <int InMode> __device__ __forceinline__ bool compose_covered(float sx, 
   if constexpr (compose_folding_source(InMode)) ok = ok && vz < 0.0f;
   return ok;
 }
+
+// The sources of an ideal lens (the Sources policy of lrp_compose_pixel.h): ray_to_source and the coverage test.
+template <int InMode> struct LensSources {
+  static constexpr bool kLoop = (InMode == kInEquirectLoop);
+  static __device__ __forceinline__ bool map(const ComposeSource &S, float vx, float vy, float vz, float in_w, float in_h, float &sx, float &sy) {
+    float px, py;
+    ray_to_source<InMode>(S.lens, in_w, in_h, vx, vy, vz, px, py);
+    sx = (px - 0.5f) + in_w * 0.5f; // src/reproject.cpp:323-324
+    sy = (py - 0.5f) + in_h * 0.5f;
+    return compose_covered<InMode>(sx, sy, vz, in_w, in_h);
+  }
+};
 
 // std::min: b where b < a
 __device__ __forceinline__ float compose_min(float a, float b) { return (b < a) ? b : a; }
@@ -160,15 +175,20 @@ template <int Interp> ComposeKernelFn compose_cell_kernel(int out_lens, int in_m
   return table[out_lens * kInModes + in_mode];
 }
 
-template <int Interp> hipError_t launch_compose_interp(ComposeParams P, int out_lens, int in_mode, hipStream_t stream) {
+// Starts kernel fn over the 32 x 8 tiles of the output, with argument block A; P is the part of A that states out_w and out_h
+// and takes tiles_x and tiles_y (A itself, or a block within it).  An empty output is no error; fn == nullptr: no such kernel.
+template <typename Args, typename Block> hipError_t launch_compose_tiles(void (*fn)(const Args), Args &A, Block &P, hipStream_t stream) {
   P.tiles_x = (P.out_w + kComposeTileW - 1) / kComposeTileW;
   P.tiles_y = (P.out_h + kComposeTileH - 1) / kComposeTileH;
   if (P.tiles_x <= 0 || P.tiles_y <= 0) return hipSuccess;
-  const ComposeKernelFn fn = compose_cell_kernel<Interp>(out_lens, in_mode);
   if (!fn) return hipErrorInvalidValue;
   const dim3 grid((unsigned)(kXcds * xcd_rows(P.tiles_y) * P.tiles_x)), block(kComposeThreads);
-  hipLaunchKernelGGL(fn, grid, block, 0, stream, P);
+  hipLaunchKernelGGL(fn, grid, block, 0, stream, A);
   return hipGetLastError();
+}
+
+template <int Interp> hipError_t launch_compose_interp(ComposeParams P, int out_lens, int in_mode, hipStream_t stream) {
+  return launch_compose_tiles(compose_cell_kernel<Interp>(out_lens, in_mode), P, P, stream);
 }
 
 } // namespace lrp

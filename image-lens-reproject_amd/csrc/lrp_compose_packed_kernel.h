@@ -4,10 +4,11 @@
 // three instantiation sets compile in parallel.
 //
 // The bytes are those of lrp_decode_pixels_device per source -> lrp_compose_device -> lrp_encode_pixels_device with float32
-// staging images of C channels in between.  It is compose_kernel's body (lrp_compose_kernel.h) with packed_kernel's two ends
-// (lrp_packed_kernel.h), and restates neither: the coverage test and min are compose_covered / compose_min, the lens math is
-// target_ray / ray_to_source, the samplers are sample<> of lrp_device.h with the decoding tap loader PackedTaps, the store is
-// store_packed.
+// staging images of C channels in between.  It is compose_kernel's body (lrp_compose_kernel.h) between packed_kernel's two ends
+// (lrp_packed_kernel.h).  The body — source loop, FIRST / MEAN / FEATHER, divide, tonemap — is written out here a second time,
+// and an edit to it there belongs here too: folded onto one function, kernels of both moved registers.
+// The leaves are restated nowhere: the coverage test and min are compose_covered / compose_min, the lens math is target_ray /
+// ray_to_source, the samplers are sample<> of lrp_device.h with the decoding tap loader PackedTaps, the store is store_packed.
 //
 // Mapping (gfx950): the 32 x 8 tile, one pixel per lane, tiles in xcd_tile() order; the wave-uniform source loop reads its
 // descriptor from kernarg with scalar loads, a source no active lane needs is skipped by a wave-wide test, FIRST leaves the

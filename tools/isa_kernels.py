@@ -4,7 +4,8 @@
   isa_kernels.py kernels <obj-dir>          one line per kernel symbol, sorted:
                                             <symbol> <hash> sgpr N spilled N vgpr N spilled N lds N scratch N <object>
   isa_kernels.py compare <dir-a> <dir-b>    the kernels of b against those of a: added, lost, present in two objects,
-                                            different in hash or resources; exit status 1 if any
+                                            different in hash or resources (with the instruction counts of both sides);
+                                            exit status 1 if any
   isa_kernels.py passes <obj-dir> <symbol>  the coefficient-tier and raw-tap pass bodies of the window kernel <symbol> (a
                                             substring of its mangled name): per body its tier, ds_read_b128, packed and
                                             non-packed VALU instructions up to the global_store_dwordx4 (coef_passes below)
@@ -375,7 +376,7 @@ def kernel_resources(co):
 
 
 def kernels(obj_dir):
-    """[(symbol, hash + resources, object)], sorted."""
+    """[(symbol, hash + resources, object, instructions)], sorted."""
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
         for name in sorted(os.listdir(obj_dir)):
@@ -386,24 +387,24 @@ def kernels(obj_dir):
                 continue
             texts = kernel_texts(co)
             for sym, res in kernel_resources(co).items():
-                rows.append((sym, hashlib.sha256(texts[sym].encode()).hexdigest()[:16] + " " + res, name))
+                rows.append((sym, hashlib.sha256(texts[sym].encode()).hexdigest()[:16] + " " + res, name, len(texts[sym].splitlines())))
     return sorted(rows)
 
 
 def unique(rows, label):
     seen, bad = {}, 0
-    for sym, what, obj in rows:
+    for sym, what, obj, count in rows:
         if sym in seen:
             print(f"in two objects of {label}: {sym} ({seen[sym][1]}, {obj})")
             bad = 1
-        seen[sym] = (what, obj)
+        seen[sym] = (what, obj, count)
     return seen, bad
 
 
 def main(argv):
     if len(argv) == 3 and argv[1] == "kernels":
         for row in kernels(argv[2]):
-            print(*row)
+            print(*row[:3])
         return 0
     if len(argv) == 4 and argv[1] == "passes":
         bodies = kernel_passes(argv[2], argv[3])
@@ -446,7 +447,7 @@ def main(argv):
             elif sym not in a:
                 print("added:", sym)
             elif a[sym][0] != b[sym][0]:
-                print(f"differs: {sym}\n  a: {a[sym][0]}\n  b: {b[sym][0]}")
+                print(f"differs: {sym}\n  a: {a[sym][0]} instructions {a[sym][2]}\n  b: {b[sym][0]} instructions {b[sym][2]}")
                 differ += 1
             else:
                 moved += a[sym][1] != b[sym][1]
