@@ -51,14 +51,27 @@ __device__ unsigned g_tier_stats[8]; // coefficient, raw, direct, corner, beyond
 constexpr int frame_loop_hoist(int in_mode, int ch) {
   return (ch == 5 || (in_mode == kInRect && ch == 3)) ? 1 : 2;
 }
-// Which of those kernels map lanes to pixels by LDS service group (lrp_win_plan.h win_lane_pixel<true>) instead of row-major.
-// The grouped map removes 40 % of the bank-conflict cycles of the coefficient tier's reads wherever it runs, but the time
+// Which lane -> pixel map of a pass (lrp_lane_map.h, lrp_win_plan.h win_lane_pixel) each of those kernels takes: row-major, or
+// one by LDS service group — rows (a group renders one output row) or patches (a group renders a 4 x 4 patch).
+// The rows map removes 40 % of the bank-conflict cycles of the coefficient tier's reads wherever it runs, but the time
 // follows only where the LDS array is the busiest unit: the RGBA kernel of the equidistant source (the headline: -1.0 % per
 // frame in bench.py, -1.3 % in kbench; fisheye -> fisheye level).  Everywhere else — 16-frame launches, us per frame,
 // profiles/r10_lds_account.txt — it is level or loses: equidistant RGB -0.5 % / +0.4 %, RGBAZ +0.9 % / +0.4 %, the panorama
 // sources +0.8 .. +1.3 % on four of five RGBA rows and +0.7 .. +1.6 % RGBAZ, the rectilinear source level.  They keep row-major.
-constexpr bool frame_loop_grouped_lanes(int in_mode, int ch) {
-  return in_mode == kInEquidistant && ch == 4;
+// The patches map removes most of what the rows map leaves under magnification (a row that steps to the next window row reads
+// one window column twice, `pitch` slots apart; the 3 x 3 texels under a patch lie on distinct banks) and costs nothing inside
+// a pass — the map is the block prologue's.  Under the raw taps of a ~1:1 mapping it is the worse of the two.  The census
+// (tools/analysis/lds_conflict_census.py), the counters and the times per instantiation: profiles/r12_lds_patch_map.txt.
+// The arguments are the opt-out hook: an instantiation that loses by a map returns another one for itself here.
+#ifndef LRP_FRAME_LOOP_LANE_MAP_ALL
+#define LRP_FRAME_LOOP_LANE_MAP_ALL (-1) // variant builds for same-box A/B timing: 0, 1, 2 give all twelve kernels that map
+#endif
+constexpr WinLaneMap frame_loop_lane_map(int in_mode, int ch) {
+  if (LRP_FRAME_LOOP_LANE_MAP_ALL >= 0) return (WinLaneMap)(LRP_FRAME_LOOP_LANE_MAP_ALL);
+  // the headline's RGBA kernel (rows before) and what else gains in the kbench rows: RGB of the same source, RGB / RGBA of the
+  // looping panorama.  RGBAZ loses under it as under rows (+0.1 .. +1.0 %), the rectilinear source is level: row-major.
+  const bool patches = (in_mode == kInEquidistant || in_mode == kInEquirectLoop) && (ch == 3 || ch == 4);
+  return patches ? kLanePatches : kLaneRowMajor;
 }
 // Which of those kernels dispatch on the tier of their block ONCE, in front of the frame loop: a block of the coefficient tier
 // (whole-block or half-block planes) then runs a frame loop of its own — the wait, precompute(), four passes without a tier
@@ -66,7 +79,7 @@ constexpr bool frame_loop_grouped_lanes(int in_mode, int ch) {
 // corner, gathers) is compiled without the coefficient tier.  The tier of the one block is the same in every frame; tested
 // per pass it cost every pass of every frame the flag tests and four to five taken branches over the other tiers' bodies.
 // All twelve take it: no 16-frame kbench row of theirs is slower for it than the parent's own spread
-// (profiles/r11_frame_loop_tier_dispatch.txt section 5).  The arguments are the opt-out hook, like frame_loop_grouped_lanes':
+// (profiles/r11_frame_loop_tier_dispatch.txt section 5).  The arguments are the opt-out hook, like frame_loop_lane_map's:
 // an instantiation that comes to lose by the dispatch keeps the one generic loop by returning false for it here.
 constexpr bool frame_loop_tier_dispatch(int in_mode, int ch) {
   (void)in_mode;
@@ -364,7 +377,7 @@ __global__ __launch_bounds__(kWinThreads, (GeoRead && OutLens == kEquirect) ? LR
   auto image_of = [&](int g) { return ((QMode == 2 ? 2 * g : g) ^ g_flip) & (QMode == 2 ? kAllMirrors : -1); };
   // workgroup tile = 16 kWinWaves x 16G (x 16 of the quadrant when mirrored): one strip per wavefront
   int prow, pcol; // this lane's pixel of a pass
-  win_lane_pixel<kOneBlock && frame_loop_grouped_lanes(InMode, CH)>(lane, prow, pcol);
+  win_lane_pixel<kOneBlock ? frame_loop_lane_map(InMode, CH) : kLaneRowMajor>(lane, prow, pcol);
   // SS: this lane's pixel of the pass (pcol; every lane of a pass lies in one output row) and its sub-sample; wave-uniform:
   // sub-samples per pixel and pixels per pass.  (The divisors are 4, 9, 16 and 2, 3, 4: a multiply and a shift.)
   const int ss_ns = SS ? Pk.num_samples : 1, ss_n = ss_ns * ss_ns, ss_npx = SS ? 64 / ss_n : kBlkW;

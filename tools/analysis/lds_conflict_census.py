@@ -13,9 +13,12 @@ tier decisions, from the oracle's source coordinates), derives the 16 read addre
 tier: the second tap row and the three planes, four consecutive slots each; raw-tap tier: four tap rows — and prints base
 and conflict cycles per pass for
   * the row-major lane -> pixel map (lane = 16 row + column),
-  * the grouped map (each service group renders one output row of the pass, quads of lanes stay four consecutive columns:
-    win_lane_pixel<true>),
-  * the grouped map with candidate window pitches: the smallest pitch >= bw that is 0 or 1 mod 16 (a row's run of slots then
+  * the rows map ("grouped": each service group renders one output row of the pass, quads of lanes stay four consecutive
+    columns: win_lane_pixel<kLaneRows>),
+  * the patches map (each service group renders one 4 x 4 patch of the pass: win_lane_pixel<kLanePatches>; under 2x
+    magnification a patch covers at most 3 x 3 source texels, whose slots lie on distinct banks at the pitches of the plan) and,
+    for the record, 8 x 2 patches,
+  * the rows map with candidate window pitches: the smallest pitch >= bw that is 0 or 1 mod 16 (a row's run of slots then
     stays on distinct banks when it steps to the next window row), taken only where the block's tier decisions survive it
     (raw + 3 planes still fit the buffer).
 
@@ -73,14 +76,26 @@ def extra_cycles_of_slots(slots):
     return extra
 
 
+LANE_MAPS = ("row_major", "rows", "patches", "patches_8x2")
+
+
 def lane_map(kind):
-    """(row, column) of every lane's pixel in a 16 x 4 pass: 'row_major' or 'grouped' (win_lane_pixel)."""
+    """(row, column) of every lane's pixel in a 16 x 4 pass (lrp_lane_map.h; win_lane_pixel): 'row_major', 'rows' (= 'grouped':
+    a service group renders one output row), 'patches' (a 4 x 4 patch) or, for the record only, 'patches_8x2' (8 columns x 2
+    rows; no kernel has it)."""
     lane = np.arange(64)
     if kind == "row_major":
         return lane // 16, lane % 16
     q = (lane >> 2) & 7
     parity = (q ^ (q >> 1) ^ (q >> 2)) & 1
-    return ((lane >> 5) << 1) | parity, ((lane >> 1) & 12) | (lane & 3)
+    group = ((lane >> 5) << 1) | parity  # the service group of the lane; q >> 1: the place of its quad among the group's four
+    if kind in ("rows", "grouped"):
+        return group, ((lane >> 1) & 12) | (lane & 3)
+    if kind == "patches":
+        return q >> 1, 4 * group + (lane & 3)
+    if kind == "patches_8x2":
+        return 2 * (lane >> 5) + (q >> 2), 8 * parity + 4 * ((q >> 1) & 1) + (lane & 3)
+    raise ValueError(kind)
 
 
 def pitch_bw_or_1(bw):
@@ -202,8 +217,9 @@ def main():
               f"{int((t_std['coef'] & ~keep).sum())} (planes would no longer fit)")
     print("base cycles per pass: 16 ds_read_b128 x 4 = 64")
     print(f"{'variant':44s} {'coef tier':>10s} {'raw tier':>10s} {'all staged':>11s}   (extra LDS cycles per pass, mean)")
-    variants = [("row-major, pitch bw | 1 (present)", "row_major", t_std), ("grouped, pitch bw | 1", "grouped", t_std),
-                ("grouped, pitch 0 / 1 mod 16 where it fits", "grouped", t_rule), ("row-major, pitch 0 / 1 mod 16 where it fits", "row_major", t_rule)]
+    variants = [("row-major, pitch bw | 1", "row_major", t_std), ("grouped, pitch bw | 1", "rows", t_std),
+                ("grouped, pitch 0 / 1 mod 16 where it fits", "rows", t_rule), ("row-major, pitch 0 / 1 mod 16 where it fits", "row_major", t_rule),
+                ("4 x 4 patches, pitch bw | 1", "patches", t_std), ("8 x 2 patches, pitch bw | 1", "patches_8x2", t_std)]
     for name, kind, t in variants:
         lrow, lcol = lane_map(kind)
         c = pass_cycles(ix, iy, p, t, lrow, lcol)
