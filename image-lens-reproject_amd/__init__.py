@@ -27,7 +27,8 @@ the pixel-to-ray inverse it uses, on the host), and
 camera_overlap(cameras, out_image, ...) -> camera_gains(stats, n) ->
 compose_cameras(..., gains=g) match the cameras' exposures: the statistic of the
 pairwise overlaps by one launch, gain compensation on the host, and compose with
-one gain per camera.
+one gain per camera; camera_overlap_packed(...) and compose_cameras_packed(...)
+do the same on 8-bit and half frames, with no float32 image in between.
 
 The directory name contains a hyphen (it is the name the build contract fixes);
 import it with importlib.import_module("image-lens-reproject_amd").
@@ -1003,6 +1004,131 @@ def compose_packed(in_images, in_format, in_datas, out_image, out_format, out_da
     del keep
     _check(st)
     return plane
+
+
+def _packed_camera_check(who, cameras, in_format, in_datas):
+    """reproject_packed()'s checks of every packed frame against its camera's size and the format's sample size; returns the
+    packed channel count.  No pointer is taken."""
+    n = len(cameras)
+    if len(in_datas) != n:
+        raise ValueError(f"{who}(): {n} cameras but {len(in_datas)} packed tensors")
+    sample_bytes = {int(PixelFormat.F32): 4, int(PixelFormat.F16): 2, int(PixelFormat.U8_GAMMA): 1}
+    fmt = int(in_format)
+    for i, (t, cam) in enumerate(zip(in_datas, cameras)):
+        name = f"in_datas[{i}]"
+        if not _is_torch(t) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{who}() takes device tensors only: {name} must be a contiguous CUDA tensor")
+        if fmt in sample_bytes and t.element_size() != sample_bytes[fmt]:
+            raise ValueError(f"{name}: elements of {t.element_size()} bytes ({t.dtype}) for a format of {sample_bytes[fmt]}-byte samples")
+        if t.dim() < 1 or t.numel() != cam.width * cam.height * t.shape[-1]:
+            raise ValueError(f"{name}: packed tensors must hold height*width pixels of shape[-1] samples")
+    if any(t.shape[-1] != in_datas[0].shape[-1] for t in in_datas[1:]):
+        raise ValueError(f"{who}(): every camera must have the same number of packed channels")
+    return int(in_datas[0].shape[-1]) if n else 0
+
+
+def _packed_camera_array(cameras, in_datas):
+    """The lrp_camera array of a packed camera call: camera i's pointer is in_datas[i]'s (after _packed_camera_check)."""
+    arr = (_native.LrpCamera * max(len(cameras), 1))(*[c.to_c() for c in cameras])
+    for i, t in enumerate(in_datas):
+        arr[i].data = t.data_ptr()
+    return arr
+
+
+def compose_cameras_packed(cameras, in_format, in_datas, out_image, out_format, out_data, out_fill, num_samples, interpolation,
+                           rotation_matrices=None, mode=ComposeMode.FIRST, post=None, count=None, coverage=None, device=None, stream=None,
+                           gains=None):
+    """lrp_compose_cameras_packed_device (include/lrp.h "calibrated cameras, packed pixels"): compose_cameras() on frames and an
+    output in their file formats, as one launch — the bytes of decode_pixels per camera -> compose_cameras(gains=) ->
+    encode_pixels without the float32 staging images.  `in_datas` (one per camera, all in `in_format` and of one packed channel
+    count) and `out_data` are contiguous CUDA tensors of shape (height, width, packed_channels) as reproject_packed() takes them;
+    the cameras give the geometry (their own data is not looked at) and out_image the lens, the size and the channel count C.
+    rotation_matrices, mode, post, count / coverage (None, True or a tensor to fill; both returned) and gains as in
+    compose_cameras().  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+
+    lib = _native.load()
+    n = len(cameras)
+    in_datas = list(in_datas)
+    in_pch = _packed_camera_check("compose_cameras_packed", cameras, in_format, in_datas)
+    sample_bytes = {int(PixelFormat.F32): 4, int(PixelFormat.F16): 2, int(PixelFormat.U8_GAMMA): 1}
+    if not _is_torch(out_data) or not out_data.is_cuda or not out_data.is_contiguous():
+        raise ValueError("compose_cameras_packed() takes device tensors only: out_data must be a contiguous CUDA tensor")
+    if int(out_format) in sample_bytes and out_data.element_size() != sample_bytes[int(out_format)]:
+        raise ValueError(f"out_data: elements of {out_data.element_size()} bytes ({out_data.dtype}) for a format of "
+                         f"{sample_bytes[int(out_format)]}-byte samples")
+    if out_data.dim() < 1 or out_data.numel() != out_image.width * out_image.height * out_data.shape[-1]:
+        raise ValueError("out_data: packed tensors must hold height*width pixels of shape[-1] samples")
+    for name, arg in (("count", count), ("coverage", coverage)):
+        if arg is None or arg is False or arg is True:
+            continue
+        if (not _is_torch(arg) or arg.dtype != torch.uint8 or not arg.is_cuda or not arg.is_contiguous()
+                or arg.numel() != out_image.height * out_image.width):
+            raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor with height*width elements")
+    g = None
+    if gains is not None:
+        g = np.ascontiguousarray(np.asarray(gains.cpu() if _is_torch(gains) else gains, dtype=np.float32).reshape(-1))
+        if g.size != n:
+            raise ValueError("gains must hold one value per camera")
+    if device is None:
+        device = out_data.device.index
+    planes = {}
+    for name, arg in (("count", count), ("coverage", coverage)):
+        planes[name] = None if arg is None or arg is False else arg
+        if arg is True:
+            planes[name] = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}")
+    arr = _packed_camera_array(cameras, in_datas)
+    cout = LrpImage()
+    cout.lens = out_image.lens.to_c()
+    cout.width, cout.height, cout.channels = out_image.width, out_image.height, out_image.channels
+    cout.data = out_data.data_ptr()
+    cout.data_layout = out_image.data_layout
+    rot, keep = None, None
+    if rotation_matrices is not None:
+        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
+        rot = keep.ctypes.data
+    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    st = lib.lrp_compose_cameras_packed_device(arr, n, int(in_format), in_pch, rot, g.ctypes.data if g is not None else None, ctypes.byref(cout),
+                                               int(out_format), int(out_data.shape[-1]), int(out_fill), int(num_samples), int(interpolation),
+                                               int(mode), ctypes.byref(cpost) if cpost is not None else None,
+                                               planes["count"].data_ptr() if planes["count"] is not None else None,
+                                               planes["coverage"].data_ptr() if planes["coverage"] is not None else None, device,
+                                               _stream_handle(stream))
+    del keep, g
+    _check(st)
+    return planes["count"], planes["coverage"]
+
+
+def camera_overlap_packed(cameras, in_format, in_datas, out_image, rotation_matrices=None, lo=0.02, hi=0.98, stats=None, device=None,
+                          stream=None):
+    """lrp_camera_overlap_packed_device (include/lrp.h "calibrated cameras, packed pixels"): camera_overlap() on frames in their
+    file formats, as one launch — the table of decode_pixels per camera -> camera_overlap(), word for word, without the float32
+    frames.  `in_datas` as in compose_cameras_packed(); out_image gives the lens, the size and the channel count C (its data is
+    not looked at).  The table feeds camera_gains() unchanged.  Asynchronous on `stream`."""
+    import torch
+
+    lib = _native.load()
+    n = len(cameras)
+    in_datas = list(in_datas)
+    in_pch = _packed_camera_check("camera_overlap_packed", cameras, in_format, in_datas)
+    if stats is not None and (not _is_torch(stats) or stats.dtype != torch.int64 or not stats.is_cuda or not stats.is_contiguous()
+                              or stats.numel() != 128):
+        raise ValueError("stats must be a contiguous int64 CUDA tensor with 8*8*2 elements")
+    if device is None:
+        device = in_datas[0].device.index if n else 0
+    if stats is None:
+        stats = torch.empty((8, 8, 2), dtype=torch.int64, device=f"cuda:{device}")
+    arr = _packed_camera_array(cameras, in_datas)
+    cout = Image(out_image.lens, out_image.width, out_image.height, out_image.channels, None).to_c()
+    rot, keep = None, None
+    if rotation_matrices is not None:
+        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
+        rot = keep.ctypes.data
+    st = lib.lrp_camera_overlap_packed_device(arr, n, int(in_format), in_pch, rot, ctypes.byref(cout), float(lo), float(hi), stats.data_ptr(),
+                                              device, _stream_handle(stream))
+    del keep
+    _check(st)
+    return stats
 
 
 def pixel_tables():

@@ -1,0 +1,43 @@
+// lrp_camera_packed.hip — calibrated cameras' packed frames composed into one packed output by one launch (include/lrp.h
+// "calibrated cameras, packed pixels"): the launcher lrp_capi.cpp calls, and the nearest-neighbour
+// instantiations of compose_cam_packed_kernel (lrp_camera_packed_kernel.h).  The bilinear ones are lrp_camera_packed_bl.hip, the
+// bicubic ones lrp_camera_packed_bc.hip (8-bit frames) and lrp_camera_packed_bc_f16.hip (half frames).
+#include <hip/hip_runtime.h>
+
+#include "lrp_camera_packed_kernel.h"
+
+namespace lrp {
+
+hipError_t launch_camera_packed_bilinear(const CameraPackedParams &P, int in_format, int out_lens, hipStream_t stream);
+hipError_t launch_camera_packed_bicubic_u8(const CameraPackedParams &P, int out_lens, hipStream_t stream);
+hipError_t launch_camera_packed_bicubic_f16(const CameraPackedParams &P, int out_lens, hipStream_t stream);
+hipError_t pixel_tables_device(int device, hipStream_t stream, const float **decode, const float **threshold); // lrp_pixel_kernels.hip
+
+// P: what lrp_capi.cpp states (lrp_camera_packed.h); the rest is derived here.  in_format: kPackedF16 / kPackedU8.
+// interpolation: 0 nearest, 1 bilinear, 2 bicubic (include/lrp.h lrp_interpolation).
+hipError_t launch_compose_cameras_packed(CameraPackedParams P, int in_format, int out_lens, int interpolation, int device, hipStream_t stream) {
+  if ((in_format != kPackedF16 && in_format != kPackedU8) || (P.out_format != kPackedF32 && P.out_format != kPackedF16 && P.out_format != kPackedU8) ||
+      P.n_src < 1 || P.n_src > kComposeMaxSources || P.channels < 1 || P.channels > kPackedMaxChannels || P.in_channels < 1 || P.out_channels < 1 ||
+      P.num_samples < 1 || P.num_samples > kComposeSsMaxSamples)
+    return hipErrorInvalidValue;
+  const hipError_t e = pixel_tables_device(device, stream, &P.decode, &P.threshold);
+  if (e != hipSuccess) return e;
+  const int in_sample = in_format == kPackedU8 ? 1 : 2, out_sample = P.out_format == kPackedU8 ? 1 : (P.out_format == kPackedF16 ? 2 : 4);
+  P.in_pitch = P.in_channels * in_sample;
+  P.out_pitch = P.out_channels * out_sample;
+  P.in_copy = P.in_channels < P.channels ? P.in_channels : P.channels;
+  P.out_copy = P.channels < P.out_channels ? P.channels : P.out_channels;
+  P.in_vec = 0u;
+  for (int i = 0; i < P.n_src; ++i) // per camera: base pointers differ in alignment within one call
+    if (P.in_channels == 4 && reinterpret_cast<uintptr_t>(P.src[i].data) % (uintptr_t)(4 * in_sample) == 0) P.in_vec |= 1u << i;
+  P.out_vec = P.out_channels == 4 && reinterpret_cast<uintptr_t>(P.dst) % (uintptr_t)(4 * out_sample) == 0;
+  P.tiles_x = (P.out_w + kComposeTileW - 1) / kComposeTileW;
+  P.tiles_y = (P.out_h + kComposeTileH - 1) / kComposeTileH;
+  if (interpolation == 0) return launch_camera_packed_interp<0>(P, in_format, out_lens, stream);
+  if (interpolation == 1) return launch_camera_packed_bilinear(P, in_format, out_lens, stream);
+  if (interpolation == 2)
+    return in_format == kPackedU8 ? launch_camera_packed_bicubic_u8(P, out_lens, stream) : launch_camera_packed_bicubic_f16(P, out_lens, stream);
+  return hipErrorInvalidValue;
+}
+
+} // namespace lrp

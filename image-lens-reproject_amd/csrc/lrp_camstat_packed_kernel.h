@@ -1,41 +1,39 @@
-// lrp_camstat_kernel.h — the camera overlap statistic (include/lrp.h "exposure matching across a camera rig", DESIGN.md section
-// 19): for every pair of cameras i, j the number of output pixels both see with a luminance inside [lo, hi], and the sum of
-// camera i's luminance over them, as 64-bit integers — one launch, no image.  Included by lrp_camstat.hip alone: the sampler
-// is fixed (bilinear), so there is one instantiation per target lens.
+// lrp_camstat_packed_kernel.h — the camera overlap statistic of packed frames (include/lrp.h "calibrated cameras, packed pixels",
+// DESIGN.md section 21): lrp_camera_overlap_device's table — for every pair of cameras i, j the number of output pixels both see
+// with a luminance inside [lo, hi], and the sum of camera i's luminance over them, as 64-bit integers — from frames of 8-bit or
+// binary16 samples, in one launch and with no float32 frame.  Included by lrp_camstat_packed.hip alone: the sampler is fixed
+// (bilinear), so there is one instantiation per target lens and source format.
 //
-// Per output pixel: the pixel centre of compose_cam_kernel (lrp_camera_kernel.h) at num_samples == 1 — target_ray, the rotation,
-// camera_project, the coverage test and sample<1> are that kernel's, restated nowhere — then Y_i, valid_i and q_i of the header.
+// It is cam_overlap_kernel (lrp_camstat_kernel.h) with the decoding tap loader PackedTaps (lrp_packed_kernel.h) in place of
+// FloatTaps; the body is written out here once more and an edit to it there belongs here too.  The luminance reads the first
+// min(C, 3) channels, so a texel is four lanes wide whatever C is, and only min(in_channels, C, 3) samples of a tap are decoded.
 //
-// Mapping (gfx950): compose_cam_kernel's 32 x 8 tile, one pixel per lane, tiles in xcd_tile() order, descriptors in SGPRs, a
-// ballot per camera so that a camera no lane sees forms no address.  What a reduction changes:
-//   - no lane returns before the end.  Lanes outside the image and workgroup numbers xcd_tile() rejects take part with every
-//     valid bit clear: the wave-wide sums and the barrier below see all 256 lanes.
-//   - the per-lane state is eight q_i and an 8-bit mask.  The mask is a register; q_i is parked in LDS, each lane in a slot of
-//     its own (8 cameras x 256 lanes x 4 bytes = 8 KB; no barrier: a lane reads back what it wrote).  The camera loop stays
-//     rolled like compose_cam_kernel's: unrolled eight times, the descriptors of all cameras are live at once and the SGPRs spill.
-//   - a workgroup walks tiles g = blockIdx.x, blockIdx.x + gridDim.x, .. and adds to memory once, at its end: at most
-//     kOverlapMaxBlocks x 2 n^2 atomic adds per launch instead of 2 n^2 per tile, all of which land in the same 1 KB.
-//   - the wave's table lives across its lanes: lane i * 8 + j owns entry (i, j) and keeps N_ij, S_ij in two 64-bit registers.
-//     N_ij of a tile is the population count of a ballot (scalar); S_ij a butterfly sum of q_i over the lanes of that ballot,
-//     in two 16-bit halves so that 64 values of up to 2^31 cannot overflow 32 bits.  A pair no lane of the wave has is skipped.
-//   - at the end the four waves' tables meet in LDS (4 waves x 128 words x 8 bytes = 4 KB), one barrier, and threads 0 .. 127 add
-//     the non-zero words with one 64-bit vector atomic each (agent scope).  LDS in all: 12 KB (kOverlapLdsBytes).
-// Integer sums: the result is the same whatever the order.  Nothing is accumulated in float.
+// Mapping (gfx950): cam_overlap_kernel's, rule by rule — no lane returns before the end, q_i is parked in LDS, the wave's table
+// lives across its lanes and is summed by butterflies, one 64-bit vector atomic per non-zero word at the workgroup's end.  What
+// is added: the 8-bit decode table in LDS (1 KiB), loaded by the 256 threads in front of the tile loop, with one barrier there.
+// LDS in all: 12 KiB for half frames, 13 KiB for 8-bit ones.
 #pragma once
 
 #include "lrp_camera_kernel.h"
-#include "lrp_camstat.h"
-#include "lrp_camstat_reduce.h" // kOverlapWaves, kOverlapLdsBytes, wave_sum_u32
+#include "lrp_camera_packed.h"
+#include "lrp_camstat_reduce.h"
+#include "lrp_packed_kernel.h"
 
 namespace lrp {
 
-using CameraStatKernelFn = void (*)(const CameraStatParams);
+using CameraStatPackedKernelFn = void (*)(const CameraStatPackedParams);
 
-template <int OutLens>
-__global__ __launch_bounds__(kComposeThreads) void cam_overlap_kernel(const CameraStatParams P) {
+template <int OutLens, int Fmt>
+__global__ __launch_bounds__(kComposeThreads) void cam_overlap_packed_kernel(const CameraStatPackedParams P) {
+  static_assert(kComposeThreads == 256, "one thread per entry of the 8-bit table");
   __shared__ unsigned long long part[kOverlapWaves][kOverlapWords];
   __shared__ uint32_t parked[kComposeMaxSources][kComposeThreads]; // q_i of this thread's pixel
+  __shared__ float lut[256];
   static_assert(sizeof(part) + sizeof(parked) == kOverlapLdsBytes, "the LDS the design states");
+  if constexpr (Fmt == kPackedU8) {
+    lut[threadIdx.x] = P.decode[threadIdx.x];
+    __syncthreads();
+  }
   const int lane = (int)(threadIdx.x % 64u), wave = (int)(threadIdx.x / 64u);
   unsigned long long acc_n = 0ull, acc_s = 0ull; // entry (lane / 8, lane % 8) of this wave's table
 
@@ -76,9 +74,13 @@ __global__ __launch_bounds__(kComposeThreads) void cam_overlap_kernel(const Came
           Q.src = S.data;
           Q.in_w = S.in_w;
           Q.in_h = S.in_h;
-          Q.channels = P.channels;
+          Q.channels = 1; // the samplers' element offsets are texel indices (PackedTaps)
           Q.ch_count = P.ch_count;
-          const Texel<0> s = sample<1, 0, false>(Q, sx, sy);
+          Texel<4> s;
+          if ((P.in_vec >> i) & 1u) // this camera's taps: one dword / 8-byte load, or one load per sample
+            s = sample<1, 4, false>(Q, sx, sy, PackedTaps<Fmt, true>{lut, (uint32_t)P.in_pitch, P.in_copy});
+          else
+            s = sample<1, 4, false>(Q, sx, sy, PackedTaps<Fmt, false>{lut, (uint32_t)P.in_pitch, P.in_copy});
           float Y = s.v[0];
           if (P.ch_count >= 3) Y = (0.25f * s.v[0] + 0.5f * s.v[1]) + 0.25f * s.v[2];
           if (Y >= P.lo && Y <= P.hi) { // false for NaN
@@ -123,13 +125,14 @@ __global__ __launch_bounds__(kComposeThreads) void cam_overlap_kernel(const Came
   }
 }
 
-template <int... OutLens>
-constexpr std::array<CameraStatKernelFn, kLensIds> camera_stat_kernel_table(std::integer_sequence<int, OutLens...>) {
-  return {{cam_overlap_kernel<OutLens>...}};
+template <int Fmt, int... OutLens>
+constexpr std::array<CameraStatPackedKernelFn, kLensIds> camera_stat_packed_kernel_table(std::integer_sequence<int, OutLens...>) {
+  return {{cam_overlap_packed_kernel<OutLens, Fmt>...}};
 }
-// The kernel of output lens out_lens; nullptr: no such lens.
-inline CameraStatKernelFn camera_stat_kernel(int out_lens) {
-  static constexpr std::array<CameraStatKernelFn, kLensIds> table = camera_stat_kernel_table(std::make_integer_sequence<int, kLensIds>{});
+// The kernel of output lens out_lens and source format Fmt; nullptr: no such lens.
+template <int Fmt> CameraStatPackedKernelFn camera_stat_packed_kernel(int out_lens) {
+  static constexpr std::array<CameraStatPackedKernelFn, kLensIds> table =
+      camera_stat_packed_kernel_table<Fmt>(std::make_integer_sequence<int, kLensIds>{});
   if (out_lens < 0 || out_lens >= kLensIds) return nullptr;
   return table[out_lens];
 }

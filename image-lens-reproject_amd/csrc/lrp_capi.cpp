@@ -23,6 +23,7 @@
 #include "../../include/lrp.h"
 #include "lrp_camera.h"
 #include "lrp_camera_inverse.h"
+#include "lrp_camera_packed.h"
 #include "lrp_camgain.h"
 #include "lrp_camstat.h"
 #include "lrp_camview.h"
@@ -66,6 +67,9 @@ __attribute__((weak)) hipError_t launch_compose_cameras_gain(const CameraGainPar
 __attribute__((weak)) hipError_t launch_packed(PackedParams P, int in_format, int out_lens, int in_mode, int interpolation, int device, hipStream_t stream);
 // lrp_compose_packed.hip, weak like launch_coverage (enqueue_compose_packed).
 __attribute__((weak)) hipError_t launch_compose_packed(ComposePackedParams P, int in_format, int out_lens, int in_mode, int interpolation, int device, hipStream_t stream);
+// lrp_camera_packed.hip and lrp_camstat_packed.hip, weak likewise (enqueue_compose_cameras_packed, enqueue_camera_overlap_packed).
+__attribute__((weak)) hipError_t launch_compose_cameras_packed(CameraPackedParams P, int in_format, int out_lens, int interpolation, int device, hipStream_t stream);
+__attribute__((weak)) hipError_t launch_camera_overlap_packed(CameraStatPackedParams P, int in_format, int out_lens, int device, hipStream_t stream);
 // lrp_lanczos.hip, weak like launch_coverage (enqueue_lanczos).
 __attribute__((weak)) hipError_t launch_lanczos(KParams P, int out_lens, int in_mode, hipStream_t stream);
 hipError_t launch_post_process(float *data, uint32_t n_pixels, int channels, float exposure, float reinhard,
@@ -1072,6 +1076,86 @@ int enqueue_compose_packed(const lrp_image *ins, int n_in, int in_format, int in
   return LRP_OK;
 }
 
+// What the packed camera calls add to the checks of their float32 parents, in the order include/lrp.h states: the formats
+// (has_out false: a call without a packed output), the packed channel counts, C, the sizes in bytes.  (Dimensions are positive:
+// the parents' checks ran.)
+int validate_cameras_packed(const lrp_camera *cams, int n_in, int in_format, int in_pch, const lrp_image *out, bool has_out, int out_format,
+                            int out_pch, const char *who, const char *instead) {
+  if (in_format == LRP_PIXEL_F32) return fail(LRP_ERR_BAD_ARG, std::string("float32 frames need no decode: call ") + instead);
+  if (!format_ok(in_format) || (has_out && !format_ok(out_format))) return fail(LRP_ERR_BAD_ARG, "unknown pixel format");
+  if (in_pch < 1 || (has_out && out_pch < 1)) return fail(LRP_ERR_BAD_ARG, "packed channel counts must be >= 1");
+  if (out->channels > lrp::kPackedMaxChannels)
+    return fail(LRP_ERR_CHANNELS, std::string(who) + " takes at most " + std::to_string(lrp::kPackedMaxChannels) + " channels");
+  bool fits = !has_out || packed_addressable(*out, out_format, out_pch);
+  for (int i = 0; i < n_in; ++i) {
+    lrp_image frame;
+    std::memset(&frame, 0, sizeof(frame));
+    frame.width = cams[i].width, frame.height = cams[i].height;
+    fits = fits && packed_addressable(frame, in_format, in_pch);
+  }
+  if (!fits) return fail(LRP_ERR_BAD_DIMS, "a packed frame or output of more than 2^31 bytes cannot be addressed (the packed camera kernels form 32-bit byte offsets)");
+  return LRP_OK;
+}
+
+// One launch of the packed camera compose kernel (lrp_camera_packed.hip); no table but the two 8-bit ones, no geometry-cache
+// entry, no allocation.  gains == nullptr: a gain of 1.0f per camera.
+int enqueue_compose_cameras_packed(const lrp_camera *cams, int n_in, int in_format, int in_pch, const float *rotations, const float *gains,
+                                   const lrp_image *out, int out_format, int out_pch, unsigned out_fill, int num_samples, int interpolation,
+                                   int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, int device, hipStream_t stream) {
+  if (!lrp::launch_compose_cameras_packed) return fail(LRP_ERR_HIP, "the packed camera compose kernels (lrp_camera_packed.hip) are not part of this build");
+  lrp::CameraPackedParams C;
+  std::memset(&C, 0, sizeof(C));
+  C.dst = out->data;
+  C.count = count;
+  C.coverage = coverage;
+  C.out_w = out->width, C.out_h = out->height, C.channels = out->channels;
+  C.in_channels = in_pch, C.out_channels = out_pch;
+  C.out_format = out_format;
+  C.out_fill = out_fill;
+  C.out_lens = pack_lens(out->lens);
+  C.has_post = post != nullptr;
+  if (post) C.exposure = post->exposure, C.reinhard = post->reinhard;
+  for (int i = 0; i < n_in; ++i) {
+    lrp::CameraSource &S = C.src[i];
+    pack_camera(S, cams[i]);
+    S.data = cams[i].data;
+    S.has_rot = rotations != nullptr;
+    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
+    C.gain[i] = gains ? gains[i] : 1.0f;
+  }
+  C.n_src = n_in;
+  C.mode = mode;
+  C.num_samples = num_samples;
+  const hipError_t e = lrp::launch_compose_cameras_packed(C, in_format, out->lens.type, interpolation, device, stream);
+  if (e != hipSuccess) return hip_fail(e, "packed camera compose kernel launch");
+  return LRP_OK;
+}
+
+// The launcher (lrp_camstat_packed.hip) zeroes the table on `stream` ahead of the one launch of the packed overlap kernel, which
+// adds into it; no allocation, no geometry-cache entry.
+int enqueue_camera_overlap_packed(const lrp_camera *cams, int n_in, int in_format, int in_pch, const float *rotations, const lrp_image *out,
+                                  float lo, float hi, uint64_t *stats, int device, hipStream_t stream) {
+  if (!lrp::launch_camera_overlap_packed) return fail(LRP_ERR_HIP, "the packed camera overlap kernels (lrp_camstat_packed.hip) are not part of this build");
+  lrp::CameraStatPackedParams C;
+  std::memset(&C, 0, sizeof(C));
+  C.stats = reinterpret_cast<unsigned long long *>(stats);
+  C.out_w = out->width, C.out_h = out->height, C.channels = out->channels;
+  C.in_channels = in_pch;
+  C.out_lens = pack_lens(out->lens);
+  C.n_src = n_in;
+  C.lo = lo, C.hi = hi;
+  for (int i = 0; i < n_in; ++i) {
+    lrp::CameraSource &S = C.src[i];
+    pack_camera(S, cams[i]);
+    S.data = cams[i].data;
+    S.has_rot = rotations != nullptr;
+    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
+  }
+  const hipError_t e = lrp::launch_camera_overlap_packed(C, in_format, out->lens.type, device, stream);
+  if (e != hipSuccess) return hip_fail(e, "zeroing the overlap table or the packed camera overlap kernel launch");
+  return LRP_OK;
+}
+
 // Grow-only device / pinned buffer.
 struct Buffer {
   void *ptr = nullptr;
@@ -1450,6 +1534,42 @@ int lrp_compose_packed_device(const lrp_image *ins, int n_in, int in_format, int
   if (st != LRP_OK) return st;
   return enqueue_compose_packed(ins, n_in, in_format, in_packed_channels, rotations, out, out_format, out_packed_channels, out_fill,
                                 interpolation, mode, post, count, device, (hipStream_t)stream);
+}
+
+int lrp_compose_cameras_packed_device(const lrp_camera *cams, int n_in, int in_format, int in_packed_channels, const float *rotations,
+                                      const float *gains, const lrp_image *out, int out_format, int out_packed_channels, unsigned out_fill,
+                                      int num_samples, int interpolation, int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage,
+                                      int device, void *stream) {
+  int st = validate_cameras_and_output(cams, n_in, out, interpolation, mode, true, false, nullptr);
+  if (st != LRP_OK) return st;
+  if (gains)
+    for (int i = 0; i < n_in; ++i)
+      if (!std::isfinite(gains[i]) || gains[i] < 0.0f)
+        return fail(LRP_ERR_BAD_ARG, "camera " + std::to_string(i) + ": gain must be finite and not negative");
+  if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
+    return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
+  st = validate_cameras_packed(cams, n_in, in_format, in_packed_channels, out, true, out_format, out_packed_channels, "lrp_compose_cameras_packed_device",
+                               "lrp_compose_cameras_device or lrp_compose_cameras_gain_device, then lrp_encode_pixels_device");
+  if (st != LRP_OK) return st;
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_compose_cameras_packed(cams, n_in, in_format, in_packed_channels, rotations, gains, out, out_format, out_packed_channels,
+                                        out_fill, num_samples, interpolation, mode, post, count, coverage, device, (hipStream_t)stream);
+}
+
+int lrp_camera_overlap_packed_device(const lrp_camera *cams, int n_in, int in_format, int in_packed_channels, const float *rotations,
+                                     const lrp_image *out, float lo, float hi, uint64_t *stats, int device, void *stream) {
+  // (no mode and a fixed sampler: items 1 and 4 see values that pass)
+  int st = validate_cameras_and_output(cams, n_in, out, LRP_BILINEAR, LRP_COMPOSE_FIRST, false, false, nullptr);
+  if (st != LRP_OK) return st;
+  if (!stats) return fail(LRP_ERR_NULL, "null stats");
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !(0.0f <= lo && lo <= hi && hi <= 32768.0f))
+    return fail(LRP_ERR_BAD_ARG, "lo and hi of an overlap call must be finite with 0 <= lo <= hi <= 32768");
+  st = validate_cameras_packed(cams, n_in, in_format, in_packed_channels, out, false, 0, 0, "lrp_camera_overlap_packed_device", "lrp_camera_overlap_device");
+  if (st != LRP_OK) return st;
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_camera_overlap_packed(cams, n_in, in_format, in_packed_channels, rotations, out, lo, hi, stats, device, (hipStream_t)stream);
 }
 
 namespace {

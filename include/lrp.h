@@ -734,7 +734,48 @@ int lrp_compose_packed_device(const lrp_image *ins, int n_in, int in_format, int
                               int out_packed_channels, unsigned out_fill, int interpolation, int mode, const lrp_post *post,
                               uint8_t *count /* out->width * out->height bytes, or NULL */, int device, void *stream);
 
-/* ---- Lanczos-3 ---------------------------------------------------------------------------- */
+/* ---- calibrated cameras, packed pixels: a rig's 8-bit and half frames measured and stitched with no float32 image -------- */
+
+/* lrp_compose_cameras_gain_device and lrp_camera_overlap_device on frames in their real formats.  cams[i].data carries a device
+ * pointer to packed samples of any alignment (each camera's own), cast to the field's type: cams[i].width x cams[i].height
+ * texels of in_packed_channels samples in in_format — one format and one packed channel count for all cameras.  out->data
+ * likewise: out->width x out->height pixels of out_packed_channels samples in out_format.  C = out->channels (at most 8) is the
+ * channel count of the float images the kernels of the chain would see.
+ *
+ * lrp_compose_cameras_packed_device.  The bytes written to out->data, count and coverage are exactly those of this chain with
+ * float32 temporaries tmp_i (one per camera) and tmp_out, each of C channels:
+ *   for each i:  lrp_decode_pixels_device(cams[i].data, in_format, in_packed_channels, tmp_i, C, ...)
+ *   lrp_compose_cameras_gain_device(tmp_0 .. -> tmp_out, rotations, gains, num_samples, interpolation, mode, post, count,
+ *                                   coverage) — lrp_compose_cameras_device where gains is NULL
+ *   lrp_encode_pixels_device(tmp_out, C, out->data, out_format, out_packed_channels, out_fill, ...)
+ * with the corner cases of lrp_compose_packed_device word for word: +0.0f taps behind in_packed_channels; out_fill behind C,
+ * also on a pixel no sub-sample of which is covered; such an m == 0 pixel is +0.0f (code 0) whatever post is; the 8-bit clamp
+ * maps NaN to 255 and -0 to 0; a NaN's sign and payload are the chain's, except that a call without gains multiplies by 1.0f,
+ * which leaves every value but a signalling NaN's quiet bit as it is (an 8-bit source cannot produce a NaN).
+ * gains is a HOST array of n_in floats, read before the call returns, or NULL.  in_format is LRP_PIXEL_F16 or
+ * LRP_PIXEL_U8_GAMMA; out_format is any of the three.  One launch.  Asynchronous on `stream`; allocates nothing, builds no
+ * table, neither reads nor writes the geometry cache; shares the device copy of the two 8-bit tables with the other packed calls
+ * (the first call on a device uploads it).
+ * Errors, all before a device is touched, in this order: items 1 to 5 of lrp_compose_cameras_device with their statuses and
+ * texts; LRP_ERR_BAD_ARG, naming the camera, for a gain that is not finite or is negative; item 6 (num_samples);
+ * LRP_ERR_BAD_ARG for in_format == LRP_PIXEL_F32 (float32 frames: lrp_compose_cameras_device or
+ * lrp_compose_cameras_gain_device, then lrp_encode_pixels_device), an unknown format or a packed channel count < 1;
+ * LRP_ERR_CHANNELS for C > 8; LRP_ERR_BAD_DIMS for a packed frame or output of more than 2^31 bytes.
+ *
+ * lrp_camera_overlap_packed_device.  The LRP_OVERLAP_WORDS words written to stats (DEVICE) are, as integers, those of
+ * lrp_decode_pixels_device per camera -> lrp_camera_overlap_device(.., out, lo, hi, stats); of `out` the lens, the size and
+ * channels (C) are read.  The table feeds lrp_camera_gains unchanged.  Errors: those of lrp_camera_overlap_device in its order,
+ * then the packed errors above (format, packed channel count, C > 8, frame size). */
+int lrp_compose_cameras_packed_device(const lrp_camera *cams, int n_in, int in_format, int in_packed_channels,
+                                      const float *rotations /* n_in x 9, or NULL */, const float *gains /* HOST, n_in, or NULL */,
+                                      const lrp_image *out, int out_format, int out_packed_channels, unsigned out_fill,
+                                      int num_samples, int interpolation, int mode, const lrp_post *post,
+                                      uint8_t *count, uint8_t *coverage, int device, void *stream);
+int lrp_camera_overlap_packed_device(const lrp_camera *cams, int n_in, int in_format, int in_packed_channels,
+                                     const float *rotations /* n_in x 9, or NULL */, const lrp_image *out /* lens, size, channels */,
+                                     float lo, float hi, uint64_t *stats /* DEVICE, LRP_OVERLAP_WORDS */, int device, void *stream);
+
+/* ---- Lanczos-3---------------------------------------------------------------------------- */
 
 /* LRP_LANCZOS3 (interpolation 3, with LRP_SAMPLER_EXT_LANCZOS3 on): a fourth sampler with a 6 x 6 footprint, the filter that
  * ffmpeg v360, Hugin, OpenCV and Pillow offer under this name.  The reference has none, so this text is the definition.
