@@ -147,6 +147,12 @@ SYMBOLS = {
         [_P(LrpCamera), ctypes.c_int, _FLOATP, _FLOATP, _P(LrpImage), ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(LrpPost), ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
     ),
+    "lrp_multiband_scratch_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(ctypes.c_size_t)]),
+    "lrp_compose_cameras_multiband_device": (
+        ctypes.c_int,
+        [_P(LrpCamera), ctypes.c_int, _FLOATP, _FLOATP, _P(LrpImage), ctypes.c_int, ctypes.c_int, _P(LrpPost), ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p],
+    ),
     "lrp_reproject_multi": (
         ctypes.c_int,
         [_P(LrpImage), _P(LrpImage), ctypes.c_int, ctypes.c_int, ctypes.c_int, _FLOATP, _P(LrpPost), _P(ctypes.c_int), ctypes.c_int],

@@ -31,6 +31,7 @@
 #include "lrp_compose_packed.h"
 #include "lrp_compose_ss.h"
 #include "lrp_geocache.h"
+#include "lrp_multiband.h"
 #include "lrp_packed.h"
 #include "lrp_params.h"
 #include "lrp_plan.h"
@@ -63,6 +64,11 @@ __attribute__((weak)) hipError_t launch_camera_view(const CameraViewParams &P, i
 // lrp_camstat.hip and lrp_camgain.hip, weak likewise (enqueue_camera_overlap, enqueue_compose_cameras_gain).
 __attribute__((weak)) hipError_t launch_camera_overlap(const CameraStatParams &P, int out_lens, hipStream_t stream);
 __attribute__((weak)) hipError_t launch_compose_cameras_gain(const CameraGainParams &G, int out_lens, int interpolation, hipStream_t stream);
+// lrp_multiband_label.hip and lrp_multiband.hip, weak likewise (enqueue_multiband).
+__attribute__((weak)) hipError_t launch_multiband_label(const MultibandLabelParams &P, int out_lens, hipStream_t stream);
+__attribute__((weak)) hipError_t launch_multiband_reduce(const MultibandReduceParams &P, int channels, hipStream_t stream);
+__attribute__((weak)) hipError_t launch_multiband_lap(const MultibandLapParams &P, int channels, hipStream_t stream);
+__attribute__((weak)) hipError_t launch_multiband_collapse(const MultibandCollapseParams &P, int channels, hipStream_t stream);
 // lrp_packed.hip, weak like launch_coverage (enqueue_packed).
 __attribute__((weak)) hipError_t launch_packed(PackedParams P, int in_format, int out_lens, int in_mode, int interpolation, int device, hipStream_t stream);
 // lrp_compose_packed.hip, weak like launch_coverage (enqueue_compose_packed).
@@ -894,6 +900,90 @@ int enqueue_compose_cameras_gain(const lrp_camera *cams, int n_in, const float *
   return LRP_OK;
 }
 
+static_assert(lrp::kMultibandMaxBands == LRP_MULTIBAND_MAX_BANDS && lrp::kMultibandNoCamera == LRP_MULTIBAND_NO_CAMERA, "lrp_multiband.h states the limits of include/lrp.h");
+
+// Multi-band blending (lrp_multiband*.hip), every launch on `stream`, in this order: the label kernel; then per camera its
+// level-0 layer by the one-camera compose kernels (FIRST, no post, no planes) into the scratch, B reduce launches and B + 1
+// Laplacian-accumulate launches; then B + 1 collapse launches from the top level down, the last of which writes the output.  No
+// allocation, no synchronisation, no table, no geometry-cache entry.
+int enqueue_multiband(const lrp_camera *cams, int n_in, const float *rotations, const float *gains, const lrp_image *out, int interpolation,
+                      int num_bands, const lrp_post *post, uint8_t *count, uint8_t *label, void *scratch, hipStream_t stream) {
+  if (!lrp::launch_multiband_label || !lrp::launch_multiband_reduce || !lrp::launch_multiband_lap || !lrp::launch_multiband_collapse)
+    return fail(LRP_ERR_HIP, "the multi-band kernels (lrp_multiband.hip, lrp_multiband_label.hip) are not part of this build");
+  const int C = out->channels, B = num_bands;
+  const lrp::MultibandLayout L = lrp::multiband_layout(out->width, out->height, C, B);
+  char *const base = static_cast<char *>(scratch);
+  const auto plane = [&](size_t at) { return reinterpret_cast<float *>(base + at); };
+  if (!label) label = reinterpret_cast<uint8_t *>(base + L.label);
+  if (!count) count = reinterpret_cast<uint8_t *>(base + L.count);
+  const int wrap = out->lens.type == LRP_EQUIRECTANGULAR && source_wraps(out->lens);
+
+  lrp::MultibandLabelParams LP;
+  std::memset(&LP, 0, sizeof(LP));
+  LP.label = label, LP.count = count;
+  LP.out_w = out->width, LP.out_h = out->height;
+  LP.n_src = n_in;
+  LP.out_lens = pack_lens(out->lens);
+  for (int i = 0; i < n_in; ++i) {
+    lrp::CameraSource &S = LP.src[i];
+    pack_camera(S, cams[i]);
+    S.has_rot = rotations != nullptr;
+    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
+  }
+  hipError_t e = lrp::launch_multiband_label(LP, out->lens.type, stream);
+  if (e != hipSuccess) return hip_fail(e, "multi-band label kernel launch");
+
+  lrp_image layer = *out; // camera i's G_0: the output's lens and size, in the scratch
+  layer.data = plane(L.g[0]);
+  for (int i = 0; i < n_in; ++i) {
+    const float *rot = rotations ? rotations + 9 * i : nullptr;
+    const int st = gains ? enqueue_compose_cameras_gain(cams + i, 1, rot, gains + i, &layer, 1, interpolation, LRP_COMPOSE_FIRST, nullptr, nullptr,
+                                                        nullptr, stream)
+                         : enqueue_compose_cameras(cams + i, 1, rot, &layer, 1, interpolation, LRP_COMPOSE_FIRST, nullptr, nullptr, nullptr, stream);
+    if (st != LRP_OK) return st;
+    for (int k = 0; k < B; ++k) {
+      lrp::MultibandReduceParams R;
+      std::memset(&R, 0, sizeof(R));
+      R.g = plane(L.g[k]), R.m = k > 0 ? plane(L.m[k]) : nullptr, R.label = k > 0 ? nullptr : label;
+      R.cg = plane(L.g[k + 1]), R.cm = plane(L.m[k + 1]);
+      R.w = L.w[k], R.h = L.h[k], R.cw = L.w[k + 1], R.ch = L.h[k + 1];
+      R.cam = i, R.wrap = wrap;
+      e = lrp::launch_multiband_reduce(R, C, stream);
+      if (e != hipSuccess) return hip_fail(e, "multi-band reduce kernel launch");
+    }
+    for (int k = 0; k <= B; ++k) {
+      lrp::MultibandLapParams A;
+      std::memset(&A, 0, sizeof(A));
+      A.g = plane(L.g[k]), A.m = k > 0 ? plane(L.m[k]) : nullptr, A.label = k > 0 ? nullptr : label;
+      A.a = plane(L.a[k]), A.s = plane(L.s[k]);
+      A.w = L.w[k], A.h = L.h[k];
+      A.top = k == B;
+      if (!A.top) A.cg = plane(L.g[k + 1]), A.cw = L.w[k + 1], A.ch = L.h[k + 1];
+      A.cam = i, A.wrap = wrap, A.first = i == 0;
+      e = lrp::launch_multiband_lap(A, C, stream);
+      if (e != hipSuccess) return hip_fail(e, "multi-band Laplacian-accumulate kernel launch");
+    }
+  }
+  for (int k = B; k >= 0; --k) {
+    lrp::MultibandCollapseParams K;
+    std::memset(&K, 0, sizeof(K));
+    K.a = plane(L.a[k]), K.s = plane(L.s[k]);
+    K.w = L.w[k], K.h = L.h[k];
+    K.top = k == B;
+    if (!K.top) K.cr = plane(L.a[k + 1]), K.cw = L.w[k + 1], K.ch = L.h[k + 1];
+    K.wrap = wrap;
+    K.dst = k == 0 ? out->data : plane(L.a[k]);
+    if (k == 0) {
+      K.label = label;
+      K.has_post = post != nullptr;
+      if (post) K.exposure = post->exposure, K.reinhard = post->reinhard;
+    }
+    e = lrp::launch_multiband_collapse(K, C, stream);
+    if (e != hipSuccess) return hip_fail(e, "multi-band collapse kernel launch");
+  }
+  return LRP_OK;
+}
+
 static_assert(lrp::kCameraInverseSteps == LRP_CAMERA_INVERSE_STEPS, "lrp_camera_inverse.h takes the step count of include/lrp.h");
 
 // lrp_camera_view_device's checks, in the order include/lrp.h states.
@@ -1436,6 +1526,38 @@ int lrp_compose_cameras_gain_device(const lrp_camera *cams, int n_in, const floa
   if (st != LRP_OK) return st;
   return enqueue_compose_cameras_gain(cams, n_in, rotations, gains, out, num_samples, interpolation, mode, post, count, coverage,
                                       (hipStream_t)stream);
+}
+
+int lrp_multiband_scratch_bytes(int width, int height, int channels, int num_bands, size_t *bytes) {
+  if (!bytes) return fail(LRP_ERR_NULL, "null bytes");
+  if (width < 1 || height < 1) return fail(LRP_ERR_BAD_DIMS, "image dimensions must be positive");
+  if (channels < 1 || channels > lrp::kMultibandMaxChannels) return fail(LRP_ERR_CHANNELS, "channels of a multi-band call must be 1 .. 4");
+  if (num_bands < 0 || num_bands > LRP_MULTIBAND_MAX_BANDS) return fail(LRP_ERR_BAD_ARG, "num_bands must be 0 .. " + std::to_string(LRP_MULTIBAND_MAX_BANDS));
+  *bytes = lrp::multiband_layout(width, height, channels, num_bands).total;
+  return LRP_OK;
+}
+
+int lrp_compose_cameras_multiband_device(const lrp_camera *cams, int n_in, const float *rotations, const float *gains, const lrp_image *out,
+                                         int interpolation, int num_bands, const lrp_post *post, uint8_t *count, uint8_t *label, void *scratch,
+                                         size_t scratch_bytes, int device, void *stream) {
+  int st = validate_cameras_and_output(cams, n_in, out, interpolation, LRP_COMPOSE_FIRST, true, false, nullptr);
+  if (st != LRP_OK) return st;
+  if (gains)
+    for (int i = 0; i < n_in; ++i)
+      if (!std::isfinite(gains[i]) || gains[i] < 0.0f)
+        return fail(LRP_ERR_BAD_ARG, "camera " + std::to_string(i) + ": gain must be finite and not negative");
+  if (out->channels > lrp::kMultibandMaxChannels) return fail(LRP_ERR_CHANNELS, "out->channels of a multi-band call must be 1 .. 4");
+  if (num_bands < 0 || num_bands > LRP_MULTIBAND_MAX_BANDS) return fail(LRP_ERR_BAD_ARG, "num_bands must be 0 .. " + std::to_string(LRP_MULTIBAND_MAX_BANDS));
+  if (!scratch) return fail(LRP_ERR_NULL, "null scratch");
+  const size_t need = lrp::multiband_layout(out->width, out->height, out->channels, num_bands).total;
+  if ((reinterpret_cast<uintptr_t>(scratch) & 255u) != 0u || scratch_bytes < need)
+    return fail(LRP_ERR_BAD_ARG, "scratch must be aligned to 256 bytes and hold what lrp_multiband_scratch_bytes states: scratch_bytes is " +
+                                     std::to_string(scratch_bytes) + ", the call needs " + std::to_string(need));
+  if (out->height > lrp::kMultibandMaxHeight)
+    return fail(LRP_ERR_BAD_DIMS, "out->height of a multi-band call must be at most " + std::to_string(lrp::kMultibandMaxHeight));
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  return enqueue_multiband(cams, n_in, rotations, gains, out, interpolation, num_bands, post, count, label, scratch, (hipStream_t)stream);
 }
 
 int lrp_camera_view_device(const lrp_camera *cams, int n_in, const float *rotations, const lrp_camera *target, float *out_data, int channels,

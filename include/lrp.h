@@ -567,6 +567,66 @@ int lrp_compose_cameras_gain_device(const lrp_camera *cams, int n_in, const floa
                                     int mode, const lrp_post *post, uint8_t *count /* out->width * out->height bytes, or NULL */,
                                     uint8_t *coverage /* out->width * out->height bytes, or NULL */, int device, void *stream);
 
+/* ---- multi-band blending across a camera rig: Laplacian-pyramid compose ---- */
+
+/* FIRST leaves a step at every seam; MEAN and FEATHER trade it for a band in which the detail of two slightly misregistered
+ * cameras is averaged into ghosts; gains with a realistic prior leave part of the exposure spread.  Burt and Adelson's multi-band
+ * blend, as Brown and Lowe and OpenCV's MultiBandBlender use it, blends low frequencies over wide zones and high frequencies over
+ * narrow ones: lrp_compose_cameras_multiband_device.  Guidance: choose num_bands so that 2^num_bands stays below the width of
+ * the overlaps.  A camera's image is zero outside its coverage, as in OpenCV; nothing is filled in.
+ *
+ * Definition, binary32, un-fused, in the order written.  W, H, C come from `out`; B = num_bands, 0 .. 8.  The level sizes are
+ * w_0 = W, w_{k+1} = (w_k + 1) >> 1, likewise h; levels 0 .. B all exist, also when a size has reached 1.
+ *
+ * Per pixel (level 0).  Camera i's covered_i, sx, sy and FEATHER weight w_i are exactly those of lrp_compose_cameras_device at
+ * num_samples == 1.  k, the number of covering cameras, goes to `count`.  The winner is the covering camera with the largest
+ * w_i: scan in ascending i, replace on w_i > best, so a tie goes to the lowest index.  `label` is the winner, or
+ * LRP_MULTIBAND_NO_CAMERA when k == 0.
+ *   G^i_0(x, y) is bit for bit what lrp_compose_cameras_gain_device(cams + i, 1, rotations + 9 i, gains + i, out, 1, interpolation,
+ *               LRP_COMPOSE_FIRST, NULL, ...) stores for the pixel; with gains == NULL what lrp_compose_cameras_device stores.  An
+ *               uncovered pixel is +0.0f.
+ *   M^i_0     = (label == i) ? 1.0f : 0.0f.
+ * Index rules.  Y_k(j) clamps j into 0 .. h_k - 1.  X_k(j) clamps likewise, except for an equirectangular target of a full turn
+ * (the decision of the wrapping sampler, taken on out->lens), where X_k(j) is j modulo w_k, non-negative.
+ * reduce (level k to k + 1, per channel and for M).  Horizontally, for x < w_{k+1}, y < h_k, with p_d = G_k(X_k(2x + d), y):
+ *   h(x, y) = (((p_-2 + p_2) + 4.0f * (p_-1 + p_1)) + 6.0f * p_0) * 0.0625f
+ * then the same expression vertically, on h(x, Y_k(2y + d)).
+ * expand, E(T), level k + 1 to k.  In one dimension, with the neighbour indices through the index rule of level k + 1:
+ *   j = 2i:      e = ((c(i - 1) + c(i + 1)) + 6.0f * c(i)) * 0.125f
+ *   j = 2i + 1:  e = (c(i) + c(i + 1)) * 0.5f
+ * horizontally first, which gives w_k x h_{k+1}, then vertically.
+ * Laplacian and accumulation.  L^i_k = G^i_k - E(G^i_{k+1}) for k < B, L^i_B = G^i_B.  A_k,c and S_k start at +0.0f; for
+ * ascending i: A_k,c = A_k,c + M^i_k * L^i_k,c (multiply, then add), S_k = S_k + M^i_k.  The product is taken as +0.0f where
+ * M^i_k == 0.0f, whatever L^i_k,c is: a camera adds nothing, not even a NaN, where its weight is zero.
+ * Collapse.  N_k,c = (S_k > 0.0f) ? A_k,c / S_k : +0.0f; R_B = N_B, R_k = N_k + E(R_{k+1}).  The pixel is R_0, then `post` on its
+ * first min(C, 3) channels.  A pixel with label == LRP_MULTIBAND_NO_CAMERA is +0.0f in every channel, whatever post is.
+ * There is no epsilon in the normalisation, so this holds exactly: with B == 0 the pixel is +0.0f + G^winner_0 — the winner's
+ * one-camera render with -0.0f turned into +0.0f, whatever the other cameras hold there.  The implementation skips work only
+ * where no bit changes.
+ *
+ * Asynchronous on `stream`; allocates nothing (the caller supplies `scratch`, DEVICE memory aligned to 256 bytes of at least
+ * lrp_multiband_scratch_bytes(W, H, C, B) bytes, whose content before and after the call means nothing), does not synchronise,
+ * builds no table, neither reads nor writes the geometry cache.  gains: HOST, n_in floats, or NULL.  count, label: W * H bytes
+ * each, or NULL.  num_samples is 1; C is 1 .. 4; the interpolation is 0 .. 2.
+ * Errors, all before a device is touched, in this order: 1. those of lrp_compose_cameras_gain_device with num_samples == 1 (no
+ * mode; gains may be NULL); 2. out->channels > 4: LRP_ERR_CHANNELS; 3. num_bands outside 0 .. 8: LRP_ERR_BAD_ARG; 4. scratch
+ * NULL: LRP_ERR_NULL; 5. scratch not aligned to 256 bytes, or scratch_bytes below the queried size: LRP_ERR_BAD_ARG with an
+ * lrp_last_error text that states both sizes; 6. out->height above 524280 (the rows a launch grid of 8-row tiles holds):
+ * LRP_ERR_BAD_DIMS.
+ *
+ * lrp_multiband_scratch_bytes (host only, pure): the exact size the call needs — one camera's pyramid (per level C floats per
+ * texel, and above level 0 the weight plane), the accumulators A_k and S_k of every level (the collapse writes R_k over A_k), and
+ * a label and a count plane, every region rounded up to 256 bytes.  Errors: bytes NULL: LRP_ERR_NULL; a size below 1:
+ * LRP_ERR_BAD_DIMS; channels outside 1 .. 4: LRP_ERR_CHANNELS; num_bands outside 0 .. 8: LRP_ERR_BAD_ARG. */
+#define LRP_MULTIBAND_MAX_BANDS 8
+#define LRP_MULTIBAND_NO_CAMERA 255
+int lrp_multiband_scratch_bytes(int width, int height, int channels, int num_bands, size_t *bytes);
+int lrp_compose_cameras_multiband_device(const lrp_camera *cams, int n_in, const float *rotations /* n_in x 9, or NULL */,
+                                         const float *gains /* HOST, n_in, or NULL */, const lrp_image *out, int interpolation,
+                                         int num_bands, const lrp_post *post, uint8_t *count /* W * H bytes, or NULL */,
+                                         uint8_t *label /* W * H bytes, or NULL */, void *scratch /* DEVICE */, size_t scratch_bytes,
+                                         int device, void *stream);
+
 /* ---- one source, several outputs, several GPUs (BASELINE configs[4]) ---------- */
 
 /* One host source, n_out host outputs (lenses in outs[i].lens, rotations + 9 * i or none): the
