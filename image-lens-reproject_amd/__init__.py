@@ -31,6 +31,8 @@ one gain per camera; camera_overlap_packed(...) and compose_cameras_packed(...)
 do the same on 8-bit and half frames, with no float32 image in between.
 compose_cameras_multiband(cameras, out_image, interpolation, ...) blends the
 cameras over a Laplacian pyramid (multi-band blending) instead of per pixel.
+compose_cameras_multiband_packed(...) does that on 8-bit and half frames into a
+packed output, again with no float32 frame or panorama.
 
 The directory name contains a hyphen (it is the name the build contract fixes);
 import it with importlib.import_module("image-lens-reproject_amd").
@@ -1198,6 +1200,73 @@ def camera_overlap_packed(cameras, in_format, in_datas, out_image, rotation_matr
     del keep
     _check(st)
     return stats
+
+
+def compose_cameras_multiband_packed(cameras, in_format, in_datas, out_image, out_format, out_data, out_fill, interpolation,
+                                     rotation_matrices=None, num_bands=5, gains=None, post=None, count=None, label=None, scratch=None,
+                                     device=None, stream=None):
+    """lrp_compose_cameras_multiband_packed_device (include/lrp.h "multi-band blending, packed pixels"): compose_cameras_multiband()
+    on frames and an output in their file formats — the bytes of decode_pixels per camera -> compose_cameras_multiband() ->
+    encode_pixels without the float32 frames and the float32 panorama.  `in_datas`, `out_data`, `out_fill` and out_image as in
+    compose_cameras_packed(); rotation_matrices, num_bands, gains, post, count / label (None, True or a tensor to fill) and scratch
+    (None allocates it; multiband_scratch_bytes() states its size) as in compose_cameras_multiband().  Returns (count, label).
+    Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+
+    lib = _native.load()
+    n = len(cameras)
+    in_datas = list(in_datas)
+    in_pch = _packed_camera_check("compose_cameras_multiband_packed", cameras, in_format, in_datas)
+    sample_bytes = {int(PixelFormat.F32): 4, int(PixelFormat.F16): 2, int(PixelFormat.U8_GAMMA): 1}
+    if not _is_torch(out_data) or not out_data.is_cuda or not out_data.is_contiguous():
+        raise ValueError("compose_cameras_multiband_packed() takes device tensors only: out_data must be a contiguous CUDA tensor")
+    if int(out_format) in sample_bytes and out_data.element_size() != sample_bytes[int(out_format)]:
+        raise ValueError(f"out_data: elements of {out_data.element_size()} bytes ({out_data.dtype}) for a format of "
+                         f"{sample_bytes[int(out_format)]}-byte samples")
+    if out_data.dim() < 1 or out_data.numel() != out_image.width * out_image.height * out_data.shape[-1]:
+        raise ValueError("out_data: packed tensors must hold height*width pixels of shape[-1] samples")
+    for name, arg in (("count", count), ("label", label)):
+        if arg is None or arg is False or arg is True:
+            continue
+        if (not _is_torch(arg) or arg.dtype != torch.uint8 or not arg.is_cuda or not arg.is_contiguous()
+                or arg.numel() != out_image.height * out_image.width):
+            raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor with height*width elements")
+    g = None
+    if gains is not None:
+        g = np.ascontiguousarray(np.asarray(gains.cpu() if _is_torch(gains) else gains, dtype=np.float32).reshape(-1))
+        if g.size != n:
+            raise ValueError("gains must hold one value per camera")
+    if device is None:
+        device = out_data.device.index
+    planes = {}
+    for name, arg in (("count", count), ("label", label)):
+        planes[name] = None if arg is None or arg is False else arg
+        if arg is True:
+            planes[name] = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}")
+    if scratch is None:
+        scratch = torch.empty(multiband_scratch_bytes(out_image.width, out_image.height, out_image.channels, num_bands), dtype=torch.uint8,
+                              device=f"cuda:{device}")
+    elif not _is_torch(scratch) or scratch.dtype != torch.uint8 or not scratch.is_cuda or not scratch.is_contiguous():
+        raise ValueError("scratch must be a contiguous uint8 CUDA tensor")
+    arr = _packed_camera_array(cameras, in_datas)
+    cout = LrpImage()
+    cout.lens = out_image.lens.to_c()
+    cout.width, cout.height, cout.channels = out_image.width, out_image.height, out_image.channels
+    cout.data = out_data.data_ptr()
+    cout.data_layout = out_image.data_layout
+    rot, keep = None, None
+    if rotation_matrices is not None:
+        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
+        rot = keep.ctypes.data
+    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    st = lib.lrp_compose_cameras_multiband_packed_device(
+        arr, n, int(in_format), in_pch, rot, g.ctypes.data if g is not None else None, ctypes.byref(cout), int(out_format),
+        int(out_data.shape[-1]), int(out_fill), int(interpolation), int(num_bands), ctypes.byref(cpost) if cpost is not None else None,
+        planes["count"].data_ptr() if planes["count"] is not None else None, planes["label"].data_ptr() if planes["label"] is not None else None,
+        scratch.data_ptr(), scratch.numel(), device, _stream_handle(stream))
+    del keep, g
+    _check(st)
+    return planes["count"], planes["label"]
 
 
 def pixel_tables():

@@ -204,6 +204,12 @@ SYMBOLS = {
         [_P(LrpCamera), ctypes.c_int, ctypes.c_int, ctypes.c_int, _FLOATP, _P(LrpImage), ctypes.c_float, ctypes.c_float, ctypes.c_void_p,
          ctypes.c_int, ctypes.c_void_p],
     ),
+    "lrp_compose_cameras_multiband_packed_device": (
+        ctypes.c_int,
+        [_P(LrpCamera), ctypes.c_int, ctypes.c_int, ctypes.c_int, _FLOATP, _FLOATP, _P(LrpImage), ctypes.c_int, ctypes.c_int, ctypes.c_uint,
+         ctypes.c_int, ctypes.c_int, _P(LrpPost), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
+         ctypes.c_void_p],
+    ),
     "lrp_decode_pixels_device": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _FLOATP, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p],

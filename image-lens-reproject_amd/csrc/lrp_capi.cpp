@@ -31,6 +31,7 @@
 #include "lrp_compose_packed.h"
 #include "lrp_compose_ss.h"
 #include "lrp_geocache.h"
+#include "lrp_mb_packed.h"
 #include "lrp_multiband.h"
 #include "lrp_packed.h"
 #include "lrp_params.h"
@@ -76,6 +77,8 @@ __attribute__((weak)) hipError_t launch_compose_packed(ComposePackedParams P, in
 // lrp_camera_packed.hip and lrp_camstat_packed.hip, weak likewise (enqueue_compose_cameras_packed, enqueue_camera_overlap_packed).
 __attribute__((weak)) hipError_t launch_compose_cameras_packed(CameraPackedParams P, int in_format, int out_lens, int interpolation, int device, hipStream_t stream);
 __attribute__((weak)) hipError_t launch_camera_overlap_packed(CameraStatPackedParams P, int in_format, int out_lens, int device, hipStream_t stream);
+// lrp_mb_packed.hip, weak likewise (enqueue_multiband with a packed side).
+__attribute__((weak)) hipError_t launch_mb_collapse_packed(MbCollapsePackedParams P, int channels, int device, hipStream_t stream);
 // lrp_lanczos.hip, weak like launch_coverage (enqueue_lanczos).
 __attribute__((weak)) hipError_t launch_lanczos(KParams P, int out_lens, int in_mode, hipStream_t stream);
 hipError_t launch_post_process(float *data, uint32_t n_pixels, int channels, float exposure, float reinhard,
@@ -902,14 +905,50 @@ int enqueue_compose_cameras_gain(const lrp_camera *cams, int n_in, const float *
 
 static_assert(lrp::kMultibandMaxBands == LRP_MULTIBAND_MAX_BANDS && lrp::kMultibandNoCamera == LRP_MULTIBAND_NO_CAMERA, "lrp_multiband.h states the limits of include/lrp.h");
 
+// Items 1 to 6 of lrp_compose_cameras_multiband_device, in the order include/lrp.h states; its packed twin runs them first.
+int validate_multiband(const lrp_camera *cams, int n_in, const float *gains, const lrp_image *out, int interpolation, int num_bands,
+                       const void *scratch, size_t scratch_bytes) {
+  const int st = validate_cameras_and_output(cams, n_in, out, interpolation, LRP_COMPOSE_FIRST, true, false, nullptr);
+  if (st != LRP_OK) return st;
+  if (gains)
+    for (int i = 0; i < n_in; ++i)
+      if (!std::isfinite(gains[i]) || gains[i] < 0.0f)
+        return fail(LRP_ERR_BAD_ARG, "camera " + std::to_string(i) + ": gain must be finite and not negative");
+  if (out->channels > lrp::kMultibandMaxChannels) return fail(LRP_ERR_CHANNELS, "out->channels of a multi-band call must be 1 .. 4");
+  if (num_bands < 0 || num_bands > LRP_MULTIBAND_MAX_BANDS) return fail(LRP_ERR_BAD_ARG, "num_bands must be 0 .. " + std::to_string(LRP_MULTIBAND_MAX_BANDS));
+  if (!scratch) return fail(LRP_ERR_NULL, "null scratch");
+  const size_t need = lrp::multiband_layout(out->width, out->height, out->channels, num_bands).total;
+  if ((reinterpret_cast<uintptr_t>(scratch) & 255u) != 0u || scratch_bytes < need)
+    return fail(LRP_ERR_BAD_ARG, "scratch must be aligned to 256 bytes and hold what lrp_multiband_scratch_bytes states: scratch_bytes is " +
+                                     std::to_string(scratch_bytes) + ", the call needs " + std::to_string(need));
+  if (out->height > lrp::kMultibandMaxHeight)
+    return fail(LRP_ERR_BAD_DIMS, "out->height of a multi-band call must be at most " + std::to_string(lrp::kMultibandMaxHeight));
+  return LRP_OK;
+}
+
 // Multi-band blending (lrp_multiband*.hip), every launch on `stream`, in this order: the label kernel; then per camera its
 // level-0 layer by the one-camera compose kernels (FIRST, no post, no planes) into the scratch, B reduce launches and B + 1
 // Laplacian-accumulate launches; then B + 1 collapse launches from the top level down, the last of which writes the output.  No
 // allocation, no synchronisation, no table, no geometry-cache entry.
+// `packed` (lrp_compose_cameras_multiband_packed_device): the frames and the output are packed.  Two launches differ: a camera's
+// level-0 layer is the one-camera packed compose kernel with a float32 output of C samples, and the level-0 collapse is
+// lrp_mb_packed.hip's, which encodes.  Both read the device copy of the two 8-bit tables, which the first packed call on a device
+// uploads; every other launch is the float call's.
+struct MultibandPacked {
+  int in_format, in_pch, out_format, out_pch;
+  unsigned out_fill;
+  int device;
+};
+int enqueue_compose_cameras_packed(const lrp_camera *cams, int n_in, int in_format, int in_pch, const float *rotations, const float *gains,
+                                   const lrp_image *out, int out_format, int out_pch, unsigned out_fill, int num_samples, int interpolation,
+                                   int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, int device, hipStream_t stream);
 int enqueue_multiband(const lrp_camera *cams, int n_in, const float *rotations, const float *gains, const lrp_image *out, int interpolation,
-                      int num_bands, const lrp_post *post, uint8_t *count, uint8_t *label, void *scratch, hipStream_t stream) {
+                      int num_bands, const lrp_post *post, uint8_t *count, uint8_t *label, void *scratch, const MultibandPacked *packed,
+                      hipStream_t stream) {
   if (!lrp::launch_multiband_label || !lrp::launch_multiband_reduce || !lrp::launch_multiband_lap || !lrp::launch_multiband_collapse)
     return fail(LRP_ERR_HIP, "the multi-band kernels (lrp_multiband.hip, lrp_multiband_label.hip) are not part of this build");
+  if (packed && !lrp::launch_mb_collapse_packed)
+    return fail(LRP_ERR_HIP, "the packed multi-band collapse kernels (lrp_mb_packed.hip) are not part of this build");
   const int C = out->channels, B = num_bands;
   const lrp::MultibandLayout L = lrp::multiband_layout(out->width, out->height, C, B);
   char *const base = static_cast<char *>(scratch);
@@ -937,9 +976,12 @@ int enqueue_multiband(const lrp_camera *cams, int n_in, const float *rotations, 
   layer.data = plane(L.g[0]);
   for (int i = 0; i < n_in; ++i) {
     const float *rot = rotations ? rotations + 9 * i : nullptr;
-    const int st = gains ? enqueue_compose_cameras_gain(cams + i, 1, rot, gains + i, &layer, 1, interpolation, LRP_COMPOSE_FIRST, nullptr, nullptr,
-                                                        nullptr, stream)
-                         : enqueue_compose_cameras(cams + i, 1, rot, &layer, 1, interpolation, LRP_COMPOSE_FIRST, nullptr, nullptr, nullptr, stream);
+    const int st = packed ? enqueue_compose_cameras_packed(cams + i, 1, packed->in_format, packed->in_pch, rot, gains ? gains + i : nullptr, &layer,
+                                                           LRP_PIXEL_F32, C, 0u, 1, interpolation, LRP_COMPOSE_FIRST, nullptr, nullptr, nullptr,
+                                                           packed->device, stream)
+                   : gains ? enqueue_compose_cameras_gain(cams + i, 1, rot, gains + i, &layer, 1, interpolation, LRP_COMPOSE_FIRST, nullptr, nullptr,
+                                                          nullptr, stream)
+                           : enqueue_compose_cameras(cams + i, 1, rot, &layer, 1, interpolation, LRP_COMPOSE_FIRST, nullptr, nullptr, nullptr, stream);
     if (st != LRP_OK) return st;
     for (int k = 0; k < B; ++k) {
       lrp::MultibandReduceParams R;
@@ -964,7 +1006,7 @@ int enqueue_multiband(const lrp_camera *cams, int n_in, const float *rotations, 
       if (e != hipSuccess) return hip_fail(e, "multi-band Laplacian-accumulate kernel launch");
     }
   }
-  for (int k = B; k >= 0; --k) {
+  for (int k = B; k >= (packed ? 1 : 0); --k) {
     lrp::MultibandCollapseParams K;
     std::memset(&K, 0, sizeof(K));
     K.a = plane(L.a[k]), K.s = plane(L.s[k]);
@@ -980,6 +1022,22 @@ int enqueue_multiband(const lrp_camera *cams, int n_in, const float *rotations, 
     }
     e = lrp::launch_multiband_collapse(K, C, stream);
     if (e != hipSuccess) return hip_fail(e, "multi-band collapse kernel launch");
+  }
+  if (packed) { // level 0, into the packed output
+    lrp::MbCollapsePackedParams K;
+    std::memset(&K, 0, sizeof(K));
+    K.a = plane(L.a[0]), K.s = plane(L.s[0]);
+    K.w = L.w[0], K.h = L.h[0];
+    K.top = B == 0;
+    if (!K.top) K.cr = plane(L.a[1]), K.cw = L.w[1], K.ch = L.h[1];
+    K.wrap = wrap;
+    K.dst = out->data;
+    K.label = label;
+    K.has_post = post != nullptr;
+    if (post) K.exposure = post->exposure, K.reinhard = post->reinhard;
+    K.out_channels = packed->out_pch, K.out_format = packed->out_format, K.out_fill = packed->out_fill;
+    e = lrp::launch_mb_collapse_packed(K, C, packed->device, stream);
+    if (e != hipSuccess) return hip_fail(e, "packed multi-band collapse kernel launch");
   }
   return LRP_OK;
 }
@@ -1540,24 +1598,11 @@ int lrp_multiband_scratch_bytes(int width, int height, int channels, int num_ban
 int lrp_compose_cameras_multiband_device(const lrp_camera *cams, int n_in, const float *rotations, const float *gains, const lrp_image *out,
                                          int interpolation, int num_bands, const lrp_post *post, uint8_t *count, uint8_t *label, void *scratch,
                                          size_t scratch_bytes, int device, void *stream) {
-  int st = validate_cameras_and_output(cams, n_in, out, interpolation, LRP_COMPOSE_FIRST, true, false, nullptr);
+  int st = validate_multiband(cams, n_in, gains, out, interpolation, num_bands, scratch, scratch_bytes);
   if (st != LRP_OK) return st;
-  if (gains)
-    for (int i = 0; i < n_in; ++i)
-      if (!std::isfinite(gains[i]) || gains[i] < 0.0f)
-        return fail(LRP_ERR_BAD_ARG, "camera " + std::to_string(i) + ": gain must be finite and not negative");
-  if (out->channels > lrp::kMultibandMaxChannels) return fail(LRP_ERR_CHANNELS, "out->channels of a multi-band call must be 1 .. 4");
-  if (num_bands < 0 || num_bands > LRP_MULTIBAND_MAX_BANDS) return fail(LRP_ERR_BAD_ARG, "num_bands must be 0 .. " + std::to_string(LRP_MULTIBAND_MAX_BANDS));
-  if (!scratch) return fail(LRP_ERR_NULL, "null scratch");
-  const size_t need = lrp::multiband_layout(out->width, out->height, out->channels, num_bands).total;
-  if ((reinterpret_cast<uintptr_t>(scratch) & 255u) != 0u || scratch_bytes < need)
-    return fail(LRP_ERR_BAD_ARG, "scratch must be aligned to 256 bytes and hold what lrp_multiband_scratch_bytes states: scratch_bytes is " +
-                                     std::to_string(scratch_bytes) + ", the call needs " + std::to_string(need));
-  if (out->height > lrp::kMultibandMaxHeight)
-    return fail(LRP_ERR_BAD_DIMS, "out->height of a multi-band call must be at most " + std::to_string(lrp::kMultibandMaxHeight));
   st = select_device(device);
   if (st != LRP_OK) return st;
-  return enqueue_multiband(cams, n_in, rotations, gains, out, interpolation, num_bands, post, count, label, scratch, (hipStream_t)stream);
+  return enqueue_multiband(cams, n_in, rotations, gains, out, interpolation, num_bands, post, count, label, scratch, nullptr, (hipStream_t)stream);
 }
 
 int lrp_camera_view_device(const lrp_camera *cams, int n_in, const float *rotations, const lrp_camera *target, float *out_data, int channels,
@@ -1677,6 +1722,26 @@ int lrp_compose_cameras_packed_device(const lrp_camera *cams, int n_in, int in_f
   if (st != LRP_OK) return st;
   return enqueue_compose_cameras_packed(cams, n_in, in_format, in_packed_channels, rotations, gains, out, out_format, out_packed_channels,
                                         out_fill, num_samples, interpolation, mode, post, count, coverage, device, (hipStream_t)stream);
+}
+
+int lrp_compose_cameras_multiband_packed_device(const lrp_camera *cams, int n_in, int in_format, int in_packed_channels, const float *rotations,
+                                                const float *gains, const lrp_image *out, int out_format, int out_packed_channels,
+                                                unsigned out_fill, int interpolation, int num_bands, const lrp_post *post, uint8_t *count,
+                                                uint8_t *label, void *scratch, size_t scratch_bytes, int device, void *stream) {
+  int st = validate_multiband(cams, n_in, gains, out, interpolation, num_bands, scratch, scratch_bytes);
+  if (st != LRP_OK) return st;
+  // (C <= 4 has passed: the packed calls' own channel item cannot fire)
+  st = validate_cameras_packed(cams, n_in, in_format, in_packed_channels, out, true, out_format, out_packed_channels,
+                               "lrp_compose_cameras_multiband_packed_device", "lrp_compose_cameras_multiband_device, then lrp_encode_pixels_device");
+  if (st != LRP_OK) return st;
+  // a camera's level-0 layer is a float32 image of C samples per pixel in the scratch, written by the packed camera kernel
+  if (!packed_addressable(*out, LRP_PIXEL_F32, out->channels))
+    return fail(LRP_ERR_BAD_DIMS, "the float32 level-0 layer of a packed multi-band call, width x height x channels x 4 bytes, must not exceed 2^31 bytes "
+                                  "(the packed camera kernels form 32-bit byte offsets)");
+  st = select_device(device);
+  if (st != LRP_OK) return st;
+  const MultibandPacked packed = {in_format, in_packed_channels, out_format, out_packed_channels, out_fill, device};
+  return enqueue_multiband(cams, n_in, rotations, gains, out, interpolation, num_bands, post, count, label, scratch, &packed, (hipStream_t)stream);
 }
 
 int lrp_camera_overlap_packed_device(const lrp_camera *cams, int n_in, int in_format, int in_packed_channels, const float *rotations,

@@ -835,6 +835,47 @@ int lrp_camera_overlap_packed_device(const lrp_camera *cams, int n_in, int in_fo
                                      const float *rotations /* n_in x 9, or NULL */, const lrp_image *out /* lens, size, channels */,
                                      float lo, float hi, uint64_t *stats /* DEVICE, LRP_OVERLAP_WORDS */, int device, void *stream);
 
+/* ---- multi-band blending, packed pixels: the blend of a rig's 8-bit and half frames with no float32 frame or panorama ------ */
+
+/* lrp_compose_cameras_multiband_device on frames and an output in their real formats; with lrp_camera_overlap_packed_device and
+ * lrp_camera_gains the chain overlap -> gains -> blend runs without a float32 copy of any frame.  cams[i].data and out->data carry
+ * packed device pointers of any alignment, as in lrp_compose_cameras_packed_device: cams[i].width x cams[i].height texels of
+ * in_packed_channels samples in in_format, out->width x out->height pixels of out_packed_channels samples in out_format.
+ * C = out->channels, 1 .. 4; num_samples is 1.
+ *
+ * Definition.  The bytes written to out->data, count and label are exactly those of this chain with float32 temporaries tmp_i
+ * (one per camera) and tmp_out, each of C channels:
+ *   for each i:  lrp_decode_pixels_device(cams[i].data, in_format, in_packed_channels, tmp_i, C, ...)
+ *   lrp_compose_cameras_multiband_device(tmp_0 .. -> tmp_out, rotations, gains, interpolation, num_bands, post, count, label,
+ *                                        scratch, ...)
+ *   lrp_encode_pixels_device(tmp_out, C, out->data, out_format, out_packed_channels, out_fill, ...)
+ * with the corner cases of lrp_compose_cameras_packed_device word for word: +0.0f taps behind in_packed_channels; out_fill behind
+ * C, also on a pixel with label == LRP_MULTIBAND_NO_CAMERA; such a pixel is +0.0f (code 0) in its first C channels whatever post
+ * is; the 8-bit clamp maps NaN to 255 and -0 to 0.  A NaN's sign and payload are the chain's: a camera's level-0 layer is
+ * lrp_compose_cameras_packed_device's with one camera, which multiplies by 1.0f where gains is NULL, but every G_0 value that
+ * reaches the output has passed M * L and an addition on both routes, which quiet a signalling NaN alike.
+ * in_format is LRP_PIXEL_F16 or LRP_PIXEL_U8_GAMMA; out_format is any of the three.
+ *
+ * scratch: what the float call needs — DEVICE memory aligned to 256 bytes of at least lrp_multiband_scratch_bytes(W, H, C, B)
+ * bytes; the pyramid stays float32.  The launches are the float call's, except that a camera's level-0 layer comes from the
+ * one-camera packed compose kernel and the last launch, the level-0 collapse, encodes.  Asynchronous on `stream`; allocates
+ * nothing, neither reads nor writes the geometry cache; shares the device copy of the two 8-bit tables with the other packed
+ * calls (the first packed call on a device uploads it: the one synchronisation).  gains: HOST, n_in floats, or NULL.
+ * Errors, all before a device is touched, in this order: items 1 to 6 of lrp_compose_cameras_multiband_device with their
+ * statuses and texts; then the packed items of lrp_compose_cameras_packed_device in its order: LRP_ERR_BAD_ARG for
+ * in_format == LRP_PIXEL_F32 (float32 frames: lrp_compose_cameras_multiband_device, then lrp_encode_pixels_device), an unknown
+ * format or a packed channel count < 1; LRP_ERR_BAD_DIMS for a packed frame or output of more than 2^31 bytes; then, this
+ * call's own, LRP_ERR_BAD_DIMS where W * H * C * 4 exceeds 2^31 bytes: a camera's level-0 layer is a float32 image of C samples
+ * per pixel in the scratch, up to four times the size of the packed output, and the packed camera kernel that writes it forms
+ * 32-bit byte offsets (C == 4: at most 2^27 pixels, e.g. 16384 x 8192). */
+int lrp_compose_cameras_multiband_packed_device(const lrp_camera *cams, int n_in, int in_format, int in_packed_channels,
+                                                const float *rotations /* n_in x 9, or NULL */,
+                                                const float *gains /* HOST, n_in, or NULL */, const lrp_image *out, int out_format,
+                                                int out_packed_channels, unsigned out_fill, int interpolation, int num_bands,
+                                                const lrp_post *post, uint8_t *count /* W * H bytes, or NULL */,
+                                                uint8_t *label /* W * H bytes, or NULL */, void *scratch /* DEVICE */,
+                                                size_t scratch_bytes, int device, void *stream);
+
 /* ---- Lanczos-3---------------------------------------------------------------------------- */
 
 /* LRP_LANCZOS3 (interpolation 3, with LRP_SAMPLER_EXT_LANCZOS3 on): a fourth sampler with a 6 x 6 footprint, the filter that
