@@ -221,6 +221,98 @@ def _rotation_arg(rotation_matrix):
     return r, r.ctypes.data
 
 
+def _rotations_arg(rotation_matrices, n):
+    """_rotation_arg for n matrices, one per source or output: (the array to keep alive across the call, its address)."""
+    if rotation_matrices is None:
+        return None, None
+    r = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
+    return r, r.ctypes.data
+
+
+def _post_arg(post):
+    """post=(exposure, reinhard) or None: (the LrpPost to keep alive across the call, its reference or None)."""
+    if post is None:
+        return None, None
+    cpost = LrpPost(float(post[0]), float(post[1]))
+    return cpost, ctypes.byref(cpost)
+
+
+def _gains_arg(gains, n):
+    """One gain per camera, a tensor or anything numpy takes, or None: (the float32 array to keep alive across the call, its
+    address)."""
+    if gains is None:
+        return None, None
+    g = np.ascontiguousarray(np.asarray(gains.cpu() if _is_torch(gains) else gains, dtype=np.float32).reshape(-1))
+    if g.size != n:
+        raise ValueError("gains must hold one value per camera")
+    return g, g.ctypes.data
+
+
+def _plane_error(name):
+    return ValueError(f"{name} must be a contiguous uint8 CUDA tensor with height*width elements")
+
+
+def _check_planes(height, width, **planes):
+    """The plane arguments of a compose call (count / coverage / label), each None or False (not wanted), True (allocate one) or
+    a tensor to fill, which is checked here — before the call looks at its images; _alloc_planes, once the device is known,
+    makes the planes."""
+    for name, arg in planes.items():
+        if arg is None or arg is False or arg is True:
+            continue
+        import torch
+
+        if not _is_torch(arg) or arg.dtype != torch.uint8 or not arg.is_cuda or not arg.is_contiguous() or arg.numel() != height * width:
+            raise _plane_error(name)
+
+
+def _alloc_planes(height, width, device, *planes):
+    """Per plane argument (after _check_planes): None, the caller's tensor, or a new (height, width) uint8 tensor on `device`."""
+    out = []
+    for arg in planes:
+        if arg is True:
+            import torch
+
+            arg = torch.empty((height, width), dtype=torch.uint8, device=f"cuda:{device}")
+        out.append(None if arg is None or arg is False else arg)
+    return out
+
+
+def _data_ptr(tensor):
+    return tensor.data_ptr() if tensor is not None else None
+
+
+def _check_stats(stats):
+    """The overlap table of a camera_overlap call, where the caller passes one."""
+    if stats is None:
+        return
+    import torch
+
+    if not _is_torch(stats) or stats.dtype != torch.int64 or not stats.is_cuda or not stats.is_contiguous() or stats.numel() != 128:
+        raise ValueError("stats must be a contiguous int64 CUDA tensor with 8*8*2 elements")
+
+
+def _stats_arg(stats, device):
+    """The caller's table (after _check_stats), or a new one on `device`."""
+    if stats is not None:
+        return stats
+    import torch
+
+    return torch.empty((8, 8, 2), dtype=torch.int64, device=f"cuda:{device}")
+
+
+def _scratch_arg(scratch, out_image, num_bands, device):
+    """The scratch of a multi-band call: the caller's tensor, checked (its size and alignment are the library's to check), or a
+    new one of multiband_scratch_bytes(...) bytes on `device`."""
+    import torch
+
+    if scratch is None:
+        return torch.empty(multiband_scratch_bytes(out_image.width, out_image.height, out_image.channels, num_bands), dtype=torch.uint8,
+                           device=f"cuda:{device}")
+    if not _is_torch(scratch) or scratch.dtype != torch.uint8 or not scratch.is_cuda or not scratch.is_contiguous():
+        raise ValueError("scratch must be a contiguous uint8 CUDA tensor")
+    return scratch
+
+
 def _stream_handle(stream):
     if stream is None:
         import torch
@@ -308,8 +400,7 @@ def reproject(in_image, out_image, num_samples, interpolation, rotation_matrix=N
     lib = _native.load()
     cin, cout = in_image.to_c(), out_image.to_c()
     keep, rot = _rotation_arg(rotation_matrix)
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
-    ppost = ctypes.byref(cpost) if cpost is not None else None
+    cpost, ppost = _post_arg(post)
     if in_image.on_device() != out_image.on_device():
         raise ValueError("input and output image data must both be on the host or both on the device")
     if in_image.on_device():
@@ -340,7 +431,7 @@ def coverage(in_image, out_image, num_samples, rotation_matrix=None, out=None, m
     if out is None:
         out = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}")
     elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() != out_image.height * out_image.width:
-        raise ValueError("out must be a contiguous uint8 CUDA tensor with height*width elements")
+        raise _plane_error("out")
     st = lib.lrp_coverage_device(ctypes.byref(cin), ctypes.byref(cout), int(num_samples), rot, out.data_ptr(), int(bool(mask_image)),
                                  int(alpha_channel), device, _stream_handle(stream))
     del keep
@@ -358,32 +449,18 @@ def compose(in_images, out_image, interpolation, rotation_matrices=None, mode=Co
     uint8 CUDA tensor of the number of covering sources per pixel) or such a tensor to fill (returned)."""
     lib = _native.load()
     n = len(in_images)
-    want_count = count is not None and count is not False
-    if want_count and count is not True:
-        import torch
-
-        if (not _is_torch(count) or count.dtype != torch.uint8 or not count.is_cuda or not count.is_contiguous()
-                or count.numel() != out_image.height * out_image.width):
-            raise ValueError("count must be a contiguous uint8 CUDA tensor with height*width elements")
+    _check_planes(out_image.height, out_image.width, count=count)
     if not out_image.on_device() or not all(i.on_device() for i in in_images):
         raise ValueError("compose() takes device tensors only: the data of every input image and of the output must be a CUDA tensor")
     if device is None:
         device = out_image.data.device.index
-    plane = None
-    if want_count:
-        import torch
-
-        plane = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}") if count is True else count
+    plane, = _alloc_planes(out_image.height, out_image.width, device, count)
     arr = (LrpImage * max(n, 1))(*[i.to_c() for i in in_images])
     cout = out_image.to_c()
-    rot, keep = None, None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
-        rot = keep.ctypes.data
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
-    st = lib.lrp_compose_device(arr, n, rot, ctypes.byref(cout), int(interpolation), int(mode),
-                                ctypes.byref(cpost) if cpost is not None else None, plane.data_ptr() if plane is not None else None,
-                                device, _stream_handle(stream))
+    keep, rot = _rotations_arg(rotation_matrices, n)
+    cpost, ppost = _post_arg(post)
+    st = lib.lrp_compose_device(arr, n, rot, ctypes.byref(cout), int(interpolation), int(mode), ppost, _data_ptr(plane), device,
+                                _stream_handle(stream))
     del keep
     _check(st)
     return plane
@@ -399,41 +476,21 @@ def compose_ss(in_images, out_image, num_samples, interpolation, rotation_matric
     num_samples^2.  Returns (count plane or None, coverage plane or None)."""
     lib = _native.load()
     n = len(in_images)
-    wanted = {}
-    for name, arg in (("count", count), ("coverage", coverage)):
-        wanted[name] = arg is not None and arg is not False
-        if wanted[name] and arg is not True:
-            import torch
-
-            if (not _is_torch(arg) or arg.dtype != torch.uint8 or not arg.is_cuda or not arg.is_contiguous()
-                    or arg.numel() != out_image.height * out_image.width):
-                raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor with height*width elements")
+    _check_planes(out_image.height, out_image.width, count=count, coverage=coverage)
     if not out_image.on_device() or not all(i.on_device() for i in in_images):
         raise ValueError("compose_ss() takes device tensors only: the data of every input image and of the output must be a CUDA tensor")
     if device is None:
         device = out_image.data.device.index
-    planes = {}
-    for name, arg in (("count", count), ("coverage", coverage)):
-        planes[name] = None
-        if wanted[name]:
-            import torch
-
-            planes[name] = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}") if arg is True else arg
+    count, coverage = _alloc_planes(out_image.height, out_image.width, device, count, coverage)
     arr = (LrpImage * max(n, 1))(*[i.to_c() for i in in_images])
     cout = out_image.to_c()
-    rot, keep = None, None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
-        rot = keep.ctypes.data
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
-    st = lib.lrp_compose_ss_device(arr, n, rot, ctypes.byref(cout), int(num_samples), int(interpolation), int(mode),
-                                   ctypes.byref(cpost) if cpost is not None else None,
-                                   planes["count"].data_ptr() if planes["count"] is not None else None,
-                                   planes["coverage"].data_ptr() if planes["coverage"] is not None else None,
-                                   device, _stream_handle(stream))
+    keep, rot = _rotations_arg(rotation_matrices, n)
+    cpost, ppost = _post_arg(post)
+    st = lib.lrp_compose_ss_device(arr, n, rot, ctypes.byref(cout), int(num_samples), int(interpolation), int(mode), ppost, _data_ptr(count),
+                                   _data_ptr(coverage), device, _stream_handle(stream))
     del keep
     _check(st)
-    return planes["count"], planes["coverage"]
+    return count, coverage
 
 
 class CameraModel(enum.IntEnum):  # include/lrp.h lrp_camera_model
@@ -512,46 +569,26 @@ def compose_cameras(cameras, out_image, num_samples, interpolation, rotation_mat
     lrp_compose_cameras_gain_device (include/lrp.h "exposure matching across a camera rig")."""
     lib = _native.load()
     n = len(cameras)
-    wanted = {}
-    for name, arg in (("count", count), ("coverage", coverage)):
-        wanted[name] = arg is not None and arg is not False
-        if wanted[name] and arg is not True:
-            import torch
-
-            if (not _is_torch(arg) or arg.dtype != torch.uint8 or not arg.is_cuda or not arg.is_contiguous()
-                    or arg.numel() != out_image.height * out_image.width):
-                raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor with height*width elements")
+    _check_planes(out_image.height, out_image.width, count=count, coverage=coverage)
     if not out_image.on_device() or not all(c.on_device() for c in cameras):
         raise ValueError("compose_cameras() takes device tensors only: the data of every camera and of the output must be a CUDA tensor")
     if device is None:
         device = out_image.data.device.index
-    planes = {}
-    for name, arg in (("count", count), ("coverage", coverage)):
-        planes[name] = None
-        if wanted[name]:
-            import torch
-
-            planes[name] = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}") if arg is True else arg
+    count, coverage = _alloc_planes(out_image.height, out_image.width, device, count, coverage)
     arr = (_native.LrpCamera * max(n, 1))(*[c.to_c(out_image.channels) for c in cameras])
     cout = out_image.to_c()
-    rot, keep = None, None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
-        rot = keep.ctypes.data
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
-    tail = (ctypes.byref(cout), int(num_samples), int(interpolation), int(mode), ctypes.byref(cpost) if cpost is not None else None,
-            planes["count"].data_ptr() if planes["count"] is not None else None,
-            planes["coverage"].data_ptr() if planes["coverage"] is not None else None, device, _stream_handle(stream))
+    keep, rot = _rotations_arg(rotation_matrices, n)
+    cpost, ppost = _post_arg(post)
+    tail = (ctypes.byref(cout), int(num_samples), int(interpolation), int(mode), ppost, _data_ptr(count), _data_ptr(coverage), device,
+            _stream_handle(stream))
     if gains is None:
         st = lib.lrp_compose_cameras_device(arr, n, rot, *tail)
     else:
-        g = np.ascontiguousarray(np.asarray(gains.cpu() if _is_torch(gains) else gains, dtype=np.float32).reshape(-1))
-        if g.size != n:
-            raise ValueError("gains must hold one value per camera")
-        st = lib.lrp_compose_cameras_gain_device(arr, n, rot, g.ctypes.data, *tail)
+        g, gains_ptr = _gains_arg(gains, n)
+        st = lib.lrp_compose_cameras_gain_device(arr, n, rot, gains_ptr, *tail)
     del keep
     _check(st)
-    return planes["count"], planes["coverage"]
+    return count, coverage
 
 
 MULTIBAND_MAX_BANDS = 8
@@ -575,50 +612,26 @@ def compose_cameras_multiband(cameras, out_image, interpolation, rotation_matric
     bytes aligned to 256, or None to allocate one.  count / label: True to allocate the plane, a uint8 CUDA tensor of
     height * width elements to fill, None to leave it out; the return value is the pair (count, label) — the number of cameras
     that cover each pixel, and the camera that wins it (MULTIBAND_NO_CAMERA where none does)."""
-    import torch
-
     lib = _native.load()
     n = len(cameras)
-    wanted = {}
-    for name, arg in (("count", count), ("label", label)):
-        wanted[name] = arg is not None and arg is not False
-        if wanted[name] and arg is not True:
-            if (not _is_torch(arg) or arg.dtype != torch.uint8 or not arg.is_cuda or not arg.is_contiguous()
-                    or arg.numel() != out_image.height * out_image.width):
-                raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor with height*width elements")
+    _check_planes(out_image.height, out_image.width, count=count, label=label)
     if not out_image.on_device() or not all(c.on_device() for c in cameras):
         raise ValueError("compose_cameras_multiband() takes device tensors only: the data of every camera and of the output must be a CUDA tensor")
     if device is None:
         device = out_image.data.device.index
-    planes = {}
-    for name, arg in (("count", count), ("label", label)):
-        planes[name] = None
-        if wanted[name]:
-            planes[name] = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}") if arg is True else arg
-    if scratch is None:
-        scratch = torch.empty(multiband_scratch_bytes(out_image.width, out_image.height, out_image.channels, num_bands), dtype=torch.uint8,
-                              device=f"cuda:{device}")
-    elif not _is_torch(scratch) or scratch.dtype != torch.uint8 or not scratch.is_cuda or not scratch.is_contiguous():
-        raise ValueError("scratch must be a contiguous uint8 CUDA tensor")
+    count, label = _alloc_planes(out_image.height, out_image.width, device, count, label)
+    scratch = _scratch_arg(scratch, out_image, num_bands, device)
     arr = (_native.LrpCamera * max(n, 1))(*[c.to_c(out_image.channels) for c in cameras])
     cout = out_image.to_c()
-    rot, keep = None, None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
-        rot = keep.ctypes.data
-    g = None
-    if gains is not None:
-        g = np.ascontiguousarray(np.asarray(gains.cpu() if _is_torch(gains) else gains, dtype=np.float32).reshape(-1))
-        if g.size != n:
-            raise ValueError("gains must hold one value per camera")
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
-    st = lib.lrp_compose_cameras_multiband_device(
-        arr, n, rot, g.ctypes.data if g is not None else None, ctypes.byref(cout), int(interpolation), int(num_bands),
-        ctypes.byref(cpost) if cpost is not None else None, planes["count"].data_ptr() if planes["count"] is not None else None,
-        planes["label"].data_ptr() if planes["label"] is not None else None, scratch.data_ptr(), scratch.numel(), device, _stream_handle(stream))
+    keep, rot = _rotations_arg(rotation_matrices, n)
+    g, gains_ptr = _gains_arg(gains, n)
+    cpost, ppost = _post_arg(post)
+    st = lib.lrp_compose_cameras_multiband_device(arr, n, rot, gains_ptr, ctypes.byref(cout), int(interpolation), int(num_bands), ppost,
+                                                  _data_ptr(count), _data_ptr(label), scratch.data_ptr(), scratch.numel(), device,
+                                                  _stream_handle(stream))
     del keep
     _check(st)
-    return planes["count"], planes["label"]
+    return count, label
 
 
 def camera_overlap(cameras, out_image, rotation_matrices=None, lo=0.02, hi=0.98, stats=None, device=None, stream=None):
@@ -627,24 +640,17 @@ def camera_overlap(cameras, out_image, rotation_matrices=None, lo=0.02, hi=0.98,
     tensor of shape (8, 8, 2) with [i, j] = (N_ij, S_ij) — the number of output pixels at which cameras i and j both have a
     luminance inside [lo, hi], and the sum of camera i's luminance over them in units of 1 / 65536.  stats: a tensor to write
     into (every word is overwritten), or None to allocate one.  Asynchronous on `stream`."""
-    import torch
-
     lib = _native.load()
     n = len(cameras)
     if not all(c.on_device() for c in cameras):
         raise ValueError("camera_overlap() takes device tensors only: the data of every camera must be a CUDA tensor")
     if device is None:
         device = cameras[0].data.device.index if n else 0
-    if stats is None:
-        stats = torch.empty((8, 8, 2), dtype=torch.int64, device=f"cuda:{device}")
-    elif not _is_torch(stats) or stats.dtype != torch.int64 or not stats.is_cuda or not stats.is_contiguous() or stats.numel() != 128:
-        raise ValueError("stats must be a contiguous int64 CUDA tensor with 8*8*2 elements")
+    _check_stats(stats)
+    stats = _stats_arg(stats, device)
     arr = (_native.LrpCamera * max(n, 1))(*[c.to_c(out_image.channels) for c in cameras])
     cout = Image(out_image.lens, out_image.width, out_image.height, out_image.channels, None).to_c()
-    rot, keep = None, None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
-        rot = keep.ctypes.data
+    keep, rot = _rotations_arg(rotation_matrices, n)
     st = lib.lrp_camera_overlap_device(arr, n, rot, ctypes.byref(cout), float(lo), float(hi), stats.data_ptr(), device, _stream_handle(stream))
     del keep
     _check(st)
@@ -680,36 +686,21 @@ def camera_view(cameras, target, out, num_samples, interpolation, rotation_matri
             or out.numel() % px != 0):
         raise ValueError("out must be a contiguous float32 CUDA tensor with height*width*channels elements")
     channels = out.numel() // px
-    wanted = {}
-    for name, arg in (("count", count), ("coverage", coverage)):
-        wanted[name] = arg is not None and arg is not False
-        if wanted[name] and arg is not True:
-            if not _is_torch(arg) or arg.dtype != torch.uint8 or not arg.is_cuda or not arg.is_contiguous() or arg.numel() != px:
-                raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor with height*width elements")
+    _check_planes(target.height, target.width, count=count, coverage=coverage)
     if not all(c.on_device() for c in cameras):
         raise ValueError("camera_view() takes device tensors only: the data of every camera must be a CUDA tensor")
     if device is None:
         device = out.device.index
-    planes = {}
-    for name, arg in (("count", count), ("coverage", coverage)):
-        planes[name] = None
-        if wanted[name]:
-            planes[name] = torch.empty((target.height, target.width), dtype=torch.uint8, device=f"cuda:{device}") if arg is True else arg
+    count, coverage = _alloc_planes(target.height, target.width, device, count, coverage)
     arr = (_native.LrpCamera * max(n, 1))(*[c.to_c(channels) for c in cameras])
     ctarget = target.to_c()
-    rot, keep = None, None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
-        rot = keep.ctypes.data
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    keep, rot = _rotations_arg(rotation_matrices, n)
+    cpost, ppost = _post_arg(post)
     st = lib.lrp_camera_view_device(arr, n, rot, ctypes.byref(ctarget), out.data_ptr(), channels, int(num_samples), int(interpolation),
-                                    int(mode), ctypes.byref(cpost) if cpost is not None else None,
-                                    planes["count"].data_ptr() if planes["count"] is not None else None,
-                                    planes["coverage"].data_ptr() if planes["coverage"] is not None else None,
-                                    device, _stream_handle(stream))
+                                    int(mode), ppost, _data_ptr(count), _data_ptr(coverage), device, _stream_handle(stream))
     del keep
     _check(st)
-    return planes["count"], planes["coverage"]
+    return count, coverage
 
 
 def camera_unproject(camera, uv):
@@ -731,15 +722,10 @@ def reproject_multi(in_image, out_images, num_samples, interpolation, rotation_m
     lib = _native.load()
     cin = in_image.to_c()
     arr = (LrpImage * len(out_images))(*[o.to_c() for o in out_images])
-    rot = None
-    keep = None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(len(out_images), 9))
-        rot = keep.ctypes.data
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    keep, rot = _rotations_arg(rotation_matrices, len(out_images))
+    cpost, ppost = _post_arg(post)
     dev = in_image.data.device.index if device is None else device
-    st = lib.lrp_reproject_multi_device(ctypes.byref(cin), arr, len(out_images), int(num_samples), int(interpolation),
-                                        rot, ctypes.byref(cpost) if cpost is not None else None, dev,
+    st = lib.lrp_reproject_multi_device(ctypes.byref(cin), arr, len(out_images), int(num_samples), int(interpolation), rot, ppost, dev,
                                         _stream_handle(stream))
     del keep
     _check(st)
@@ -751,11 +737,10 @@ def reproject_rows(in_image, out_image, num_samples, interpolation, row_first, r
     lib = _native.load()
     cin, cout = in_image.to_c(), out_image.to_c()
     keep, rot = _rotation_arg(rotation_matrix)
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    cpost, ppost = _post_arg(post)
     dev = in_image.data.device.index if device is None else device
-    st = lib.lrp_reproject_rows_device(ctypes.byref(cin), ctypes.byref(cout), int(num_samples), int(interpolation), rot,
-                                       ctypes.byref(cpost) if cpost is not None else None, int(row_first), int(row_count), dev,
-                                       _stream_handle(stream))
+    st = lib.lrp_reproject_rows_device(ctypes.byref(cin), ctypes.byref(cout), int(num_samples), int(interpolation), rot, ppost,
+                                       int(row_first), int(row_count), dev, _stream_handle(stream))
     del keep
     _check(st)
 
@@ -765,14 +750,11 @@ def reproject_multi_gpu(in_image, out_images, num_samples, interpolation, rotati
     lib = _native.load()
     cin = in_image.to_c()
     arr = (LrpImage * len(out_images))(*[o.to_c() for o in out_images])
-    rot, keep = None, None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(len(out_images), 9))
-        rot = keep.ctypes.data
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    keep, rot = _rotations_arg(rotation_matrices, len(out_images))
+    cpost, ppost = _post_arg(post)
     devs = (ctypes.c_int * len(devices))(*[int(d) for d in devices])
-    st = lib.lrp_reproject_multi(ctypes.byref(cin), arr, len(out_images), int(num_samples), int(interpolation), rot,
-                                 ctypes.byref(cpost) if cpost is not None else None, devs, len(devices))
+    st = lib.lrp_reproject_multi(ctypes.byref(cin), arr, len(out_images), int(num_samples), int(interpolation), rot, ppost, devs,
+                                 len(devices))
     del keep
     _check(st)
 
@@ -788,15 +770,11 @@ def reproject_batch(in_images, out_images, num_samples, interpolation, rotation_
         return
     ins = (LrpImage * len(in_images))(*[i.to_c() for i in in_images])
     outs = (LrpImage * len(out_images))(*[o.to_c() for o in out_images])
-    rot = None
-    keep = None
-    if rotation_matrix is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrix, dtype=np.float32).reshape(9))
-        rot = keep.ctypes.data
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    keep, rot = _rotation_arg(rotation_matrix)
+    cpost, ppost = _post_arg(post)
     dev = in_images[0].data.device.index if device is None else device
-    st = lib.lrp_reproject_batch_device(ins, outs, len(in_images), int(num_samples), int(interpolation), rot,
-                                        ctypes.byref(cpost) if cpost is not None else None, dev, _stream_handle(stream))
+    st = lib.lrp_reproject_batch_device(ins, outs, len(in_images), int(num_samples), int(interpolation), rot, ppost, dev,
+                                        _stream_handle(stream))
     del keep
     _check(st)
 
@@ -854,10 +832,10 @@ class BatchContext:
     def submit(self, in_image, out_image, num_samples, interpolation, rotation_matrix=None, post=None):
         cin, cout = in_image.to_c(), out_image.to_c()
         keep, rot = _rotation_arg(rotation_matrix)
-        cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+        cpost, ppost = _post_arg(post)
         self._keep.append((in_image, out_image, keep))
         _check(self._lib.lrp_context_submit(self._h, ctypes.byref(cin), ctypes.byref(cout), int(num_samples),
-                                            int(interpolation), rot, ctypes.byref(cpost) if cpost else None))
+                                            int(interpolation), rot, ppost))
 
     def submit_packed(self, in_image, in_format, in_data, out_image, out_format, out_data, out_fill, num_samples,
                       interpolation, rotation_matrix=None, post=None):
@@ -868,13 +846,13 @@ class BatchContext:
         cin.data = in_data.ctypes.data
         cout.data = out_data.ctypes.data
         keep, rot = _rotation_arg(rotation_matrix)
-        cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+        cpost, ppost = _post_arg(post)
         ticket = ctypes.c_int(-1)
         self._keep.append((in_data, out_data, keep))
         _check(self._lib.lrp_context_submit_packed(self._h, ctypes.byref(cin), int(in_format), int(in_data.shape[-1]),
                                                    ctypes.byref(cout), int(out_format), int(out_data.shape[-1]),
-                                                   int(out_fill), int(num_samples), int(interpolation), rot,
-                                                   ctypes.byref(cpost) if cpost else None, ctypes.byref(ticket)))
+                                                   int(out_fill), int(num_samples), int(interpolation), rot, ppost,
+                                                   ctypes.byref(ticket)))
         return ticket.value
 
     def set_outside(self, mask_image=False, alpha_channel=-1):
@@ -980,6 +958,35 @@ def encode_pixels(src, dst, dst_format, fill=0, stream=None):
                                         int(fill), n, src.device.index, _stream_handle(stream)))
 
 
+# the kernels address a packed tensor by its format's sample size: a tensor of narrower elements would be read or written past
+# its end (an unknown format is left to the library's own LRP_ERR_BAD_ARG)
+_SAMPLE_BYTES = {int(PixelFormat.F32): 4, int(PixelFormat.F16): 2, int(PixelFormat.U8_GAMMA): 1}
+
+
+def _packed_tensor_check(who, tensors):
+    """The three checks of every packed tensor of the call who(), tensor by tensor: on the device and contiguous, elements of the
+    format's sample size, height * width pixels of shape[-1] samples.  tensors: (name, tensor, format, the image or camera that
+    has the width and the height) each.  One call per list, not per tensor: the mirrors' time shows in the small launches."""
+    for name, t, fmt, sized in tensors:
+        if not _is_torch(t) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{who}() takes device tensors only: {name} must be a contiguous CUDA tensor")
+        fmt = int(fmt)
+        if fmt in _SAMPLE_BYTES and t.element_size() != _SAMPLE_BYTES[fmt]:
+            raise ValueError(f"{name}: elements of {t.element_size()} bytes ({t.dtype}) for a format of {_SAMPLE_BYTES[fmt]}-byte samples")
+        if t.dim() < 1 or t.numel() != sized.width * sized.height * t.shape[-1]:
+            raise ValueError(f"{name}: packed tensors must hold height*width pixels of shape[-1] samples")
+
+
+def _packed_image(image, tensor):
+    """The lrp_image of a packed call: image's lens, size and channel count around tensor's pointer (image.data is not looked at)."""
+    c = LrpImage()
+    c.lens = image.lens.to_c()
+    c.width, c.height, c.channels = image.width, image.height, image.channels
+    c.data = tensor.data_ptr()
+    c.data_layout = image.data_layout
+    return c
+
+
 def reproject_packed(in_image, in_format, in_data, out_image, out_format, out_data, out_fill, num_samples, interpolation,
                      rotation_matrix=None, post=None, device=None, stream=None):
     """lrp_reproject_packed_device (include/lrp.h "packed pixels"): BatchContext.submit_packed's decode, reproject and encode as
@@ -988,30 +995,24 @@ def reproject_packed(in_image, in_format, in_data, out_image, out_format, out_da
     describe the float geometry (their own data is not looked at).  The output bytes are those of decode_pixels -> reproject
     -> encode_pixels.  Asynchronous on `stream` (default: torch's current stream)."""
     lib = _native.load()
+    # _packed_tensor_check's checks in this call's own order and wording — every tensor's first check, then every tensor's second,
+    # then the third without the tensor's name — which it has had since it was the only packed call
     for name, t in (("in_data", in_data), ("out_data", out_data)):
         if not _is_torch(t) or not t.is_cuda or not t.is_contiguous():
             raise ValueError(f"reproject_packed() takes device tensors only: {name} must be a contiguous CUDA tensor")
-    # the kernel addresses the tensors by the format's sample size: a tensor of narrower elements would be read or written
-    # past its end (an unknown format is left to the library's own LRP_ERR_BAD_ARG)
-    sample_bytes = {int(PixelFormat.F32): 4, int(PixelFormat.F16): 2, int(PixelFormat.U8_GAMMA): 1}
     for name, t, fmt in (("in_data", in_data, int(in_format)), ("out_data", out_data, int(out_format))):
-        if fmt in sample_bytes and t.element_size() != sample_bytes[fmt]:
-            raise ValueError(f"{name}: elements of {t.element_size()} bytes ({t.dtype}) for a format of {sample_bytes[fmt]}-byte samples")
+        if fmt in _SAMPLE_BYTES and t.element_size() != _SAMPLE_BYTES[fmt]:
+            raise ValueError(f"{name}: elements of {t.element_size()} bytes ({t.dtype}) for a format of {_SAMPLE_BYTES[fmt]}-byte samples")
     if (in_data.numel() != in_image.width * in_image.height * in_data.shape[-1]
             or out_data.numel() != out_image.width * out_image.height * out_data.shape[-1]):
         raise ValueError("packed tensors must hold height*width pixels of shape[-1] samples")
-    cin, cout = LrpImage(), LrpImage()
-    for c, im, t in ((cin, in_image, in_data), (cout, out_image, out_data)):
-        c.lens = im.lens.to_c()
-        c.width, c.height, c.channels = im.width, im.height, im.channels
-        c.data = t.data_ptr()
-        c.data_layout = im.data_layout
+    cin, cout = _packed_image(in_image, in_data), _packed_image(out_image, out_data)
     keep, rot = _rotation_arg(rotation_matrix)
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    cpost, ppost = _post_arg(post)
     dev = in_data.device.index if device is None else device
     st = lib.lrp_reproject_packed_device(ctypes.byref(cin), int(in_format), int(in_data.shape[-1]), ctypes.byref(cout), int(out_format),
-                                         int(out_data.shape[-1]), int(out_fill), int(num_samples), int(interpolation), rot,
-                                         ctypes.byref(cpost) if cpost is not None else None, dev, _stream_handle(stream))
+                                         int(out_data.shape[-1]), int(out_fill), int(num_samples), int(interpolation), rot, ppost, dev,
+                                         _stream_handle(stream))
     del keep
     _check(st)
 
@@ -1031,47 +1032,20 @@ def compose_packed(in_images, in_format, in_datas, out_image, out_format, out_da
         raise ValueError(f"compose_packed(): {n} source images but {len(in_datas)} packed tensors")
     named = [(f"in_datas[{i}]", t, int(in_format), im) for i, (t, im) in enumerate(zip(in_datas, in_images))]
     named.append(("out_data", out_data, int(out_format), out_image))
-    # reproject_packed()'s checks, for every tensor
-    sample_bytes = {int(PixelFormat.F32): 4, int(PixelFormat.F16): 2, int(PixelFormat.U8_GAMMA): 1}
-    for name, t, fmt, im in named:
-        if not _is_torch(t) or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"compose_packed() takes device tensors only: {name} must be a contiguous CUDA tensor")
-        if fmt in sample_bytes and t.element_size() != sample_bytes[fmt]:
-            raise ValueError(f"{name}: elements of {t.element_size()} bytes ({t.dtype}) for a format of {sample_bytes[fmt]}-byte samples")
-        if t.dim() < 1 or t.numel() != im.width * im.height * t.shape[-1]:
-            raise ValueError(f"{name}: packed tensors must hold height*width pixels of shape[-1] samples")
+    _packed_tensor_check("compose_packed", named)
     if any(t.shape[-1] != in_datas[0].shape[-1] for t in in_datas[1:]):
         raise ValueError("compose_packed(): every source must have the same number of packed channels")
-    want_count = count is not None and count is not False
-    if want_count and count is not True:
-        import torch
-
-        if (not _is_torch(count) or count.dtype != torch.uint8 or not count.is_cuda or not count.is_contiguous()
-                or count.numel() != out_image.height * out_image.width):
-            raise ValueError("count must be a contiguous uint8 CUDA tensor with height*width elements")
+    _check_planes(out_image.height, out_image.width, count=count)
     if device is None:
         device = out_data.device.index
-    plane = None
-    if want_count:
-        import torch
-
-        plane = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}") if count is True else count
-    arr = (LrpImage * max(n, 1))()
-    cout = LrpImage()
-    for c, im, t in [(arr[i], im, t) for i, (im, t) in enumerate(zip(in_images, in_datas))] + [(cout, out_image, out_data)]:
-        c.lens = im.lens.to_c()
-        c.width, c.height, c.channels = im.width, im.height, im.channels
-        c.data = t.data_ptr()
-        c.data_layout = im.data_layout
-    rot, keep = None, None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
-        rot = keep.ctypes.data
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    plane, = _alloc_planes(out_image.height, out_image.width, device, count)
+    arr = (LrpImage * max(n, 1))(*[_packed_image(im, t) for im, t in zip(in_images, in_datas)])
+    cout = _packed_image(out_image, out_data)
+    keep, rot = _rotations_arg(rotation_matrices, n)
+    cpost, ppost = _post_arg(post)
     st = lib.lrp_compose_packed_device(arr, n, int(in_format), int(in_datas[0].shape[-1]) if n else 0, rot, ctypes.byref(cout), int(out_format),
-                                       int(out_data.shape[-1]), int(out_fill), int(interpolation), int(mode),
-                                       ctypes.byref(cpost) if cpost is not None else None, plane.data_ptr() if plane is not None else None,
-                                       device, _stream_handle(stream))
+                                       int(out_data.shape[-1]), int(out_fill), int(interpolation), int(mode), ppost, _data_ptr(plane), device,
+                                       _stream_handle(stream))
     del keep
     _check(st)
     return plane
@@ -1083,16 +1057,8 @@ def _packed_camera_check(who, cameras, in_format, in_datas):
     n = len(cameras)
     if len(in_datas) != n:
         raise ValueError(f"{who}(): {n} cameras but {len(in_datas)} packed tensors")
-    sample_bytes = {int(PixelFormat.F32): 4, int(PixelFormat.F16): 2, int(PixelFormat.U8_GAMMA): 1}
     fmt = int(in_format)
-    for i, (t, cam) in enumerate(zip(in_datas, cameras)):
-        name = f"in_datas[{i}]"
-        if not _is_torch(t) or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"{who}() takes device tensors only: {name} must be a contiguous CUDA tensor")
-        if fmt in sample_bytes and t.element_size() != sample_bytes[fmt]:
-            raise ValueError(f"{name}: elements of {t.element_size()} bytes ({t.dtype}) for a format of {sample_bytes[fmt]}-byte samples")
-        if t.dim() < 1 or t.numel() != cam.width * cam.height * t.shape[-1]:
-            raise ValueError(f"{name}: packed tensors must hold height*width pixels of shape[-1] samples")
+    _packed_tensor_check(who, ((f"in_datas[{i}]", t, fmt, cam) for i, (t, cam) in enumerate(zip(in_datas, cameras))))
     if any(t.shape[-1] != in_datas[0].shape[-1] for t in in_datas[1:]):
         raise ValueError(f"{who}(): every camera must have the same number of packed channels")
     return int(in_datas[0].shape[-1]) if n else 0
@@ -1116,58 +1082,26 @@ def compose_cameras_packed(cameras, in_format, in_datas, out_image, out_format, 
     the cameras give the geometry (their own data is not looked at) and out_image the lens, the size and the channel count C.
     rotation_matrices, mode, post, count / coverage (None, True or a tensor to fill; both returned) and gains as in
     compose_cameras().  Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-
     lib = _native.load()
     n = len(cameras)
     in_datas = list(in_datas)
     in_pch = _packed_camera_check("compose_cameras_packed", cameras, in_format, in_datas)
-    sample_bytes = {int(PixelFormat.F32): 4, int(PixelFormat.F16): 2, int(PixelFormat.U8_GAMMA): 1}
-    if not _is_torch(out_data) or not out_data.is_cuda or not out_data.is_contiguous():
-        raise ValueError("compose_cameras_packed() takes device tensors only: out_data must be a contiguous CUDA tensor")
-    if int(out_format) in sample_bytes and out_data.element_size() != sample_bytes[int(out_format)]:
-        raise ValueError(f"out_data: elements of {out_data.element_size()} bytes ({out_data.dtype}) for a format of "
-                         f"{sample_bytes[int(out_format)]}-byte samples")
-    if out_data.dim() < 1 or out_data.numel() != out_image.width * out_image.height * out_data.shape[-1]:
-        raise ValueError("out_data: packed tensors must hold height*width pixels of shape[-1] samples")
-    for name, arg in (("count", count), ("coverage", coverage)):
-        if arg is None or arg is False or arg is True:
-            continue
-        if (not _is_torch(arg) or arg.dtype != torch.uint8 or not arg.is_cuda or not arg.is_contiguous()
-                or arg.numel() != out_image.height * out_image.width):
-            raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor with height*width elements")
-    g = None
-    if gains is not None:
-        g = np.ascontiguousarray(np.asarray(gains.cpu() if _is_torch(gains) else gains, dtype=np.float32).reshape(-1))
-        if g.size != n:
-            raise ValueError("gains must hold one value per camera")
+    _packed_tensor_check("compose_cameras_packed", (("out_data", out_data, out_format, out_image),))
+    _check_planes(out_image.height, out_image.width, count=count, coverage=coverage)
+    g, gains_ptr = _gains_arg(gains, n)
     if device is None:
         device = out_data.device.index
-    planes = {}
-    for name, arg in (("count", count), ("coverage", coverage)):
-        planes[name] = None if arg is None or arg is False else arg
-        if arg is True:
-            planes[name] = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}")
+    count, coverage = _alloc_planes(out_image.height, out_image.width, device, count, coverage)
     arr = _packed_camera_array(cameras, in_datas)
-    cout = LrpImage()
-    cout.lens = out_image.lens.to_c()
-    cout.width, cout.height, cout.channels = out_image.width, out_image.height, out_image.channels
-    cout.data = out_data.data_ptr()
-    cout.data_layout = out_image.data_layout
-    rot, keep = None, None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
-        rot = keep.ctypes.data
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
-    st = lib.lrp_compose_cameras_packed_device(arr, n, int(in_format), in_pch, rot, g.ctypes.data if g is not None else None, ctypes.byref(cout),
-                                               int(out_format), int(out_data.shape[-1]), int(out_fill), int(num_samples), int(interpolation),
-                                               int(mode), ctypes.byref(cpost) if cpost is not None else None,
-                                               planes["count"].data_ptr() if planes["count"] is not None else None,
-                                               planes["coverage"].data_ptr() if planes["coverage"] is not None else None, device,
-                                               _stream_handle(stream))
+    cout = _packed_image(out_image, out_data)
+    keep, rot = _rotations_arg(rotation_matrices, n)
+    cpost, ppost = _post_arg(post)
+    st = lib.lrp_compose_cameras_packed_device(arr, n, int(in_format), in_pch, rot, gains_ptr, ctypes.byref(cout), int(out_format),
+                                               int(out_data.shape[-1]), int(out_fill), int(num_samples), int(interpolation), int(mode), ppost,
+                                               _data_ptr(count), _data_ptr(coverage), device, _stream_handle(stream))
     del keep, g
     _check(st)
-    return planes["count"], planes["coverage"]
+    return count, coverage
 
 
 def camera_overlap_packed(cameras, in_format, in_datas, out_image, rotation_matrices=None, lo=0.02, hi=0.98, stats=None, device=None,
@@ -1176,25 +1110,17 @@ def camera_overlap_packed(cameras, in_format, in_datas, out_image, rotation_matr
     file formats, as one launch — the table of decode_pixels per camera -> camera_overlap(), word for word, without the float32
     frames.  `in_datas` as in compose_cameras_packed(); out_image gives the lens, the size and the channel count C (its data is
     not looked at).  The table feeds camera_gains() unchanged.  Asynchronous on `stream`."""
-    import torch
-
     lib = _native.load()
     n = len(cameras)
     in_datas = list(in_datas)
     in_pch = _packed_camera_check("camera_overlap_packed", cameras, in_format, in_datas)
-    if stats is not None and (not _is_torch(stats) or stats.dtype != torch.int64 or not stats.is_cuda or not stats.is_contiguous()
-                              or stats.numel() != 128):
-        raise ValueError("stats must be a contiguous int64 CUDA tensor with 8*8*2 elements")
+    _check_stats(stats)  # (before the device is looked for, as the planes of the compose calls are)
     if device is None:
         device = in_datas[0].device.index if n else 0
-    if stats is None:
-        stats = torch.empty((8, 8, 2), dtype=torch.int64, device=f"cuda:{device}")
+    stats = _stats_arg(stats, device)
     arr = _packed_camera_array(cameras, in_datas)
     cout = Image(out_image.lens, out_image.width, out_image.height, out_image.channels, None).to_c()
-    rot, keep = None, None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
-        rot = keep.ctypes.data
+    keep, rot = _rotations_arg(rotation_matrices, n)
     st = lib.lrp_camera_overlap_packed_device(arr, n, int(in_format), in_pch, rot, ctypes.byref(cout), float(lo), float(hi), stats.data_ptr(),
                                               device, _stream_handle(stream))
     del keep
@@ -1211,62 +1137,28 @@ def compose_cameras_multiband_packed(cameras, in_format, in_datas, out_image, ou
     compose_cameras_packed(); rotation_matrices, num_bands, gains, post, count / label (None, True or a tensor to fill) and scratch
     (None allocates it; multiband_scratch_bytes() states its size) as in compose_cameras_multiband().  Returns (count, label).
     Asynchronous on `stream` (default: torch's current stream)."""
-    import torch
-
     lib = _native.load()
     n = len(cameras)
     in_datas = list(in_datas)
     in_pch = _packed_camera_check("compose_cameras_multiband_packed", cameras, in_format, in_datas)
-    sample_bytes = {int(PixelFormat.F32): 4, int(PixelFormat.F16): 2, int(PixelFormat.U8_GAMMA): 1}
-    if not _is_torch(out_data) or not out_data.is_cuda or not out_data.is_contiguous():
-        raise ValueError("compose_cameras_multiband_packed() takes device tensors only: out_data must be a contiguous CUDA tensor")
-    if int(out_format) in sample_bytes and out_data.element_size() != sample_bytes[int(out_format)]:
-        raise ValueError(f"out_data: elements of {out_data.element_size()} bytes ({out_data.dtype}) for a format of "
-                         f"{sample_bytes[int(out_format)]}-byte samples")
-    if out_data.dim() < 1 or out_data.numel() != out_image.width * out_image.height * out_data.shape[-1]:
-        raise ValueError("out_data: packed tensors must hold height*width pixels of shape[-1] samples")
-    for name, arg in (("count", count), ("label", label)):
-        if arg is None or arg is False or arg is True:
-            continue
-        if (not _is_torch(arg) or arg.dtype != torch.uint8 or not arg.is_cuda or not arg.is_contiguous()
-                or arg.numel() != out_image.height * out_image.width):
-            raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor with height*width elements")
-    g = None
-    if gains is not None:
-        g = np.ascontiguousarray(np.asarray(gains.cpu() if _is_torch(gains) else gains, dtype=np.float32).reshape(-1))
-        if g.size != n:
-            raise ValueError("gains must hold one value per camera")
+    _packed_tensor_check("compose_cameras_multiband_packed", (("out_data", out_data, out_format, out_image),))
+    _check_planes(out_image.height, out_image.width, count=count, label=label)
+    g, gains_ptr = _gains_arg(gains, n)
     if device is None:
         device = out_data.device.index
-    planes = {}
-    for name, arg in (("count", count), ("label", label)):
-        planes[name] = None if arg is None or arg is False else arg
-        if arg is True:
-            planes[name] = torch.empty((out_image.height, out_image.width), dtype=torch.uint8, device=f"cuda:{device}")
-    if scratch is None:
-        scratch = torch.empty(multiband_scratch_bytes(out_image.width, out_image.height, out_image.channels, num_bands), dtype=torch.uint8,
-                              device=f"cuda:{device}")
-    elif not _is_torch(scratch) or scratch.dtype != torch.uint8 or not scratch.is_cuda or not scratch.is_contiguous():
-        raise ValueError("scratch must be a contiguous uint8 CUDA tensor")
+    count, label = _alloc_planes(out_image.height, out_image.width, device, count, label)
+    scratch = _scratch_arg(scratch, out_image, num_bands, device)
     arr = _packed_camera_array(cameras, in_datas)
-    cout = LrpImage()
-    cout.lens = out_image.lens.to_c()
-    cout.width, cout.height, cout.channels = out_image.width, out_image.height, out_image.channels
-    cout.data = out_data.data_ptr()
-    cout.data_layout = out_image.data_layout
-    rot, keep = None, None
-    if rotation_matrices is not None:
-        keep = np.ascontiguousarray(np.asarray(rotation_matrices, dtype=np.float32).reshape(n, 9))
-        rot = keep.ctypes.data
-    cpost = LrpPost(float(post[0]), float(post[1])) if post is not None else None
+    cout = _packed_image(out_image, out_data)
+    keep, rot = _rotations_arg(rotation_matrices, n)
+    cpost, ppost = _post_arg(post)
     st = lib.lrp_compose_cameras_multiband_packed_device(
-        arr, n, int(in_format), in_pch, rot, g.ctypes.data if g is not None else None, ctypes.byref(cout), int(out_format),
-        int(out_data.shape[-1]), int(out_fill), int(interpolation), int(num_bands), ctypes.byref(cpost) if cpost is not None else None,
-        planes["count"].data_ptr() if planes["count"] is not None else None, planes["label"].data_ptr() if planes["label"] is not None else None,
-        scratch.data_ptr(), scratch.numel(), device, _stream_handle(stream))
+        arr, n, int(in_format), in_pch, rot, gains_ptr, ctypes.byref(cout), int(out_format), int(out_data.shape[-1]), int(out_fill),
+        int(interpolation), int(num_bands), ppost, _data_ptr(count), _data_ptr(label), scratch.data_ptr(), scratch.numel(), device,
+        _stream_handle(stream))
     del keep, g
     _check(st)
-    return planes["count"], planes["label"]
+    return count, label
 
 
 def pixel_tables():

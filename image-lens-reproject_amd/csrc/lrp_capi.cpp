@@ -639,14 +639,52 @@ const char *in_mode_name(int mode) {
   }
 }
 
-// lrp_compose_device's checks, in the order include/lrp.h states.
-int validate_compose(const lrp_image *ins, int n_in, const lrp_image *out, int interpolation, int mode) {
+// The checks that several compose and camera entry points run, each stated once; where and in which order
+// an entry point runs them is its validator's business (include/lrp.h states the order).
+// Item 1 of every compose call: n_in, then mode.
+int check_sources_and_mode(int n_in, int mode) {
   if (n_in < 1 || n_in > LRP_COMPOSE_MAX_SOURCES)
     return fail(LRP_ERR_BAD_ARG, "n_in of a compose call must be 1 .. " + std::to_string(LRP_COMPOSE_MAX_SOURCES));
   if (mode != LRP_COMPOSE_FIRST && mode != LRP_COMPOSE_MEAN && mode != LRP_COMPOSE_FEATHER) return fail(LRP_ERR_BAD_ARG, "unknown compose mode");
+  return LRP_OK;
+}
+
+int check_compose_samples(int num_samples) {
+  if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
+    return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
+  return LRP_OK;
+}
+
+// The sampler of a camera call: the reference's three (validate() knows LRP_LANCZOS3 besides).
+int check_three_samplers(int interpolation) {
+  if (interpolation != LRP_NEAREST && interpolation != LRP_BILINEAR && interpolation != LRP_BICUBIC)
+    return fail(LRP_ERR_INTERPOLATION, "Interpolation method not supported.");
+  return LRP_OK;
+}
+
+// gains: n_in values (not null).
+int check_gains(const float *gains, int n_in) {
+  for (int i = 0; i < n_in; ++i)
+    if (!std::isfinite(gains[i]) || gains[i] < 0.0f)
+      return fail(LRP_ERR_BAD_ARG, "camera " + std::to_string(i) + ": gain must be finite and not negative");
+  return LRP_OK;
+}
+
+// What an overlap call checks behind its cameras and its output.
+int check_overlap(const uint64_t *stats, float lo, float hi) {
+  if (!stats) return fail(LRP_ERR_NULL, "null stats");
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !(0.0f <= lo && lo <= hi && hi <= 32768.0f))
+    return fail(LRP_ERR_BAD_ARG, "lo and hi of an overlap call must be finite with 0 <= lo <= hi <= 32768");
+  return LRP_OK;
+}
+
+// lrp_compose_device's checks, in the order include/lrp.h states.
+int validate_compose(const lrp_image *ins, int n_in, const lrp_image *out, int interpolation, int mode) {
+  int st = check_sources_and_mode(n_in, mode);
+  if (st != LRP_OK) return st;
   if (!ins || !out) return fail(LRP_ERR_NULL, "null image");
   for (int i = 0; i < n_in; ++i) { // (in->channels == out->channels is one of validate()'s checks)
-    const int st = validate(ins + i, out, interpolation, true, false);
+    st = validate(ins + i, out, interpolation, true, false);
     if (st != LRP_OK) return st;
   }
   const int first = in_lens_mode(ins[0].lens);
@@ -657,20 +695,21 @@ int validate_compose(const lrp_image *ins, int n_in, const lrp_image *out, int i
   return LRP_OK;
 }
 
-// One launch of the compose kernel per group of 8 channels (lrp_compose.hip); no table, no geometry-cache entry, no allocation.
-int enqueue_compose(const lrp_image *ins, int n_in, const float *rotations, const lrp_image *out, int interpolation, int mode,
-                    const lrp_post *post, uint8_t *count, hipStream_t stream) {
-  if (!lrp::launch_compose) return fail(LRP_ERR_HIP, "the compose kernels (lrp_compose.hip) are not part of this build");
-  lrp::ComposeParams C;
-  std::memset(&C, 0, sizeof(C));
-  for (int i = 0; i < n_in; ++i) { // the per-source values as make_params() packs them for a reprojection of source i
+// The ideal-lens sources of a compose block (ComposeParams, ComposeSsParams, ComposePackedParams; the block must be zeroed): per
+// source the values make_params() packs for a reprojection of source i — none of those taken depends on num_samples — and its data
+// pointer; the output's size, lens and tonemap from source 0; n_src and mode.
+template <class Block>
+void pack_ideal_sources(Block &C, const lrp_image *ins, int n_in, const float *rotations, const lrp_image *out, int mode, const lrp_post *post) {
+  for (int i = 0; i < n_in; ++i) {
     const lrp::KParams P = make_params(ins + i, out, 1, rotations ? rotations + 9 * i : nullptr, post);
     if (i == 0) {
       C.out_w = P.out_w, C.out_h = P.out_h, C.channels = P.channels;
       C.out_lens = P.out_lens;
+      C.has_post = P.has_post;
       C.exposure = P.exposure, C.reinhard = P.reinhard;
     }
-    lrp::ComposeSource &S = C.src[i];
+    auto &S = C.src[i];
+    S.data = ins[i].data;
     S.in_w = P.in_w, S.in_h = P.in_h;
     S.lens = P.in_lens;
     S.has_rot = P.has_rot;
@@ -678,17 +717,38 @@ int enqueue_compose(const lrp_image *ins, int n_in, const float *rotations, cons
   }
   C.n_src = n_in;
   C.mode = mode;
-  const int channels = out->channels, group = lrp::kComposeMaxChannels;
+}
+
+// One launch per group of 8 channels of a float32 compose block whose sources (src[i].data: channel 0 of source i) and n_src are
+// packed: the loop moves the sources' pointers and dst to the group's first channel and states ch_count and has_post, launch(c0)
+// enqueues the block as it then stands.  `what` names the launch in lrp_last_error.
+template <class Block, class Launch>
+int launch_channel_groups(Block &C, float *dst, int channels, const lrp_post *post, const char *what, Launch launch) {
+  const float *base[lrp::kComposeMaxSources];
+  for (int i = 0; i < C.n_src; ++i) base[i] = C.src[i].data;
+  const int group = lrp::kComposeMaxChannels;
   for (int c0 = 0; c0 < channels; c0 += group) {
-    for (int i = 0; i < n_in; ++i) C.src[i].data = ins[i].data + c0;
-    C.dst = out->data + c0;
+    for (int i = 0; i < C.n_src; ++i) C.src[i].data = base[i] + c0;
+    C.dst = dst + c0;
     C.ch_count = std::min(group, channels - c0);
     C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
-    C.count = c0 == 0 ? count : nullptr;
-    const hipError_t e = lrp::launch_compose(C, out->lens.type, in_lens_mode(ins[0].lens), interpolation, stream);
-    if (e != hipSuccess) return hip_fail(e, "compose kernel launch");
+    const hipError_t e = launch(c0);
+    if (e != hipSuccess) return hip_fail(e, what);
   }
   return LRP_OK;
+}
+
+// One launch of the compose kernel per group of 8 channels (lrp_compose.hip); no table, no geometry-cache entry, no allocation.
+int enqueue_compose(const lrp_image *ins, int n_in, const float *rotations, const lrp_image *out, int interpolation, int mode,
+                    const lrp_post *post, uint8_t *count, hipStream_t stream) {
+  if (!lrp::launch_compose) return fail(LRP_ERR_HIP, "the compose kernels (lrp_compose.hip) are not part of this build");
+  lrp::ComposeParams C;
+  std::memset(&C, 0, sizeof(C));
+  pack_ideal_sources(C, ins, n_in, rotations, out, mode, post);
+  return launch_channel_groups(C, out->data, out->channels, post, "compose kernel launch", [&](int c0) {
+    C.count = c0 == 0 ? count : nullptr; // (k does not depend on the channels: the first group writes it)
+    return lrp::launch_compose(C, out->lens.type, in_lens_mode(ins[0].lens), interpolation, stream);
+  });
 }
 
 // One launch of the supersampled compose kernel per group of 8 channels (lrp_compose_ss.hip), each of which writes the planes;
@@ -698,34 +758,13 @@ int enqueue_compose_ss(const lrp_image *ins, int n_in, const float *rotations, c
   if (!lrp::launch_compose_ss) return fail(LRP_ERR_HIP, "the supersampled compose kernels (lrp_compose_ss.hip) are not part of this build");
   lrp::ComposeSsParams C;
   std::memset(&C, 0, sizeof(C));
-  for (int i = 0; i < n_in; ++i) { // the per-source values as make_params() packs them for a reprojection of source i
-    const lrp::KParams P = make_params(ins + i, out, num_samples, rotations ? rotations + 9 * i : nullptr, post);
-    if (i == 0) {
-      C.out_w = P.out_w, C.out_h = P.out_h, C.channels = P.channels;
-      C.out_lens = P.out_lens;
-      C.exposure = P.exposure, C.reinhard = P.reinhard;
-    }
-    lrp::ComposeSource &S = C.src[i];
-    S.in_w = P.in_w, S.in_h = P.in_h;
-    S.lens = P.in_lens;
-    S.has_rot = P.has_rot;
-    std::memcpy(S.rot, P.rot, sizeof(S.rot));
-  }
-  C.n_src = n_in;
-  C.mode = mode;
+  pack_ideal_sources(C, ins, n_in, rotations, out, mode, post);
   C.num_samples = num_samples;
   C.count = count;
   C.coverage = coverage;
-  const int channels = out->channels, group = lrp::kComposeMaxChannels;
-  for (int c0 = 0; c0 < channels; c0 += group) {
-    for (int i = 0; i < n_in; ++i) C.src[i].data = ins[i].data + c0;
-    C.dst = out->data + c0;
-    C.ch_count = std::min(group, channels - c0);
-    C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
-    const hipError_t e = lrp::launch_compose_ss(C, out->lens.type, in_lens_mode(ins[0].lens), interpolation, stream);
-    if (e != hipSuccess) return hip_fail(e, "supersampled compose kernel launch");
-  }
-  return LRP_OK;
+  return launch_channel_groups(C, out->data, out->channels, post, "supersampled compose kernel launch", [&](int) {
+    return lrp::launch_compose_ss(C, out->lens.type, in_lens_mode(ins[0].lens), interpolation, stream);
+  });
 }
 
 static_assert((int)lrp::kCameraBrown == LRP_CAMERA_BROWN && (int)lrp::kCameraFisheye == LRP_CAMERA_FISHEYE, "lrp_camera.h numbers camera models like include/lrp.h");
@@ -768,9 +807,8 @@ int validate_camera(const lrp_camera &cam, const std::string &who, int channels,
 // (lrp_camera_overlap_device).
 int validate_cameras_and_output(const lrp_camera *cams, int n_in, const lrp_image *out, int interpolation, int mode, bool needs_out_data,
                                 bool wants_gains, const float *gains) {
-  if (n_in < 1 || n_in > LRP_COMPOSE_MAX_SOURCES)
-    return fail(LRP_ERR_BAD_ARG, "n_in of a compose call must be 1 .. " + std::to_string(LRP_COMPOSE_MAX_SOURCES));
-  if (mode != LRP_COMPOSE_FIRST && mode != LRP_COMPOSE_MEAN && mode != LRP_COMPOSE_FEATHER) return fail(LRP_ERR_BAD_ARG, "unknown compose mode");
+  int st = check_sources_and_mode(n_in, mode);
+  if (st != LRP_OK) return st;
   if (!cams || !out) return fail(LRP_ERR_NULL, cams ? "null image" : "null camera array");
   if (wants_gains && !gains) return fail(LRP_ERR_NULL, "null gains");
   if (!lens_in_hot_path(out->lens.type, g_lens_ext.load(std::memory_order_relaxed))) return fail(LRP_ERR_OUTPUT_LENS, "Output lens type not supported.");
@@ -778,10 +816,10 @@ int validate_cameras_and_output(const lrp_camera *cams, int n_in, const lrp_imag
   if (out->width < 1 || out->height < 1) return fail(LRP_ERR_BAD_DIMS, "image dimensions must be positive");
   if (!image_addressable(*out)) return fail(LRP_ERR_BAD_DIMS, "an image of more than 2^31 floats (8 GiB) cannot be addressed");
   if (needs_out_data && !out->data) return fail(LRP_ERR_NULL, "null image data");
-  if (interpolation != LRP_NEAREST && interpolation != LRP_BILINEAR && interpolation != LRP_BICUBIC)
-    return fail(LRP_ERR_INTERPOLATION, "Interpolation method not supported.");
+  st = check_three_samplers(interpolation);
+  if (st != LRP_OK) return st;
   for (int i = 0; i < n_in; ++i) {
-    const int st = validate_camera(cams[i], "camera " + std::to_string(i) + ": ", out->channels, true);
+    st = validate_camera(cams[i], "camera " + std::to_string(i) + ": ", out->channels, true);
     if (st != LRP_OK) return st;
   }
   return LRP_OK;
@@ -791,9 +829,7 @@ int validate_cameras_and_output(const lrp_camera *cams, int n_in, const lrp_imag
 int validate_compose_cameras(const lrp_camera *cams, int n_in, const lrp_image *out, int num_samples, int interpolation, int mode) {
   const int st = validate_cameras_and_output(cams, n_in, out, interpolation, mode, true, false, nullptr);
   if (st != LRP_OK) return st;
-  if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
-    return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
-  return LRP_OK;
+  return check_compose_samples(num_samples);
 }
 
 // What the kernels read of a camera besides its data pointer and its rotation.
@@ -805,6 +841,32 @@ void pack_camera(lrp::CameraSource &S, const lrp_camera &cam) {
   S.limit = cam.limit;
 }
 
+// The camera descriptors of a block (zeroed), whole: pack_camera, the data pointer — channel 0; launch_channel_groups moves it —
+// and camera i's rotation, rotations + 9 * i.
+void pack_cameras(lrp::CameraSource src[], const lrp_camera *cams, int n_in, const float *rotations) {
+  for (int i = 0; i < n_in; ++i) {
+    lrp::CameraSource &S = src[i];
+    pack_camera(S, cams[i]);
+    S.data = cams[i].data;
+    S.has_rot = rotations != nullptr;
+    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
+  }
+}
+
+// The fields the camera compose blocks share besides their descriptors (CameraParams, CameraGainParams::cam, CameraViewParams,
+// CameraPackedParams; the block must be zeroed): the output's size, the tonemap's constants, n_src, mode, num_samples and the planes.
+template <class Block>
+void set_camera_fields(Block &C, int out_w, int out_h, int channels, int n_in, int mode, int num_samples, const lrp_post *post, uint8_t *count,
+                       uint8_t *coverage) {
+  C.out_w = out_w, C.out_h = out_h, C.channels = channels;
+  if (post) C.exposure = post->exposure, C.reinhard = post->reinhard;
+  C.n_src = n_in;
+  C.mode = mode;
+  C.num_samples = num_samples;
+  C.count = count;
+  C.coverage = coverage;
+}
+
 // One launch of the camera compose kernel per group of 8 channels (lrp_camera.hip), each of which writes the planes; no table, no
 // geometry-cache entry, no allocation.
 int enqueue_compose_cameras(const lrp_camera *cams, int n_in, const float *rotations, const lrp_image *out, int num_samples, int interpolation,
@@ -812,30 +874,11 @@ int enqueue_compose_cameras(const lrp_camera *cams, int n_in, const float *rotat
   if (!lrp::launch_compose_cameras) return fail(LRP_ERR_HIP, "the camera compose kernels (lrp_camera.hip) are not part of this build");
   lrp::CameraParams C;
   std::memset(&C, 0, sizeof(C));
-  C.out_w = out->width, C.out_h = out->height, C.channels = out->channels;
+  set_camera_fields(C, out->width, out->height, out->channels, n_in, mode, num_samples, post, count, coverage);
   C.out_lens = pack_lens(out->lens);
-  if (post) C.exposure = post->exposure, C.reinhard = post->reinhard;
-  for (int i = 0; i < n_in; ++i) {
-    lrp::CameraSource &S = C.src[i];
-    pack_camera(S, cams[i]);
-    S.has_rot = rotations != nullptr;
-    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
-  }
-  C.n_src = n_in;
-  C.mode = mode;
-  C.num_samples = num_samples;
-  C.count = count;
-  C.coverage = coverage;
-  const int channels = out->channels, group = lrp::kComposeMaxChannels;
-  for (int c0 = 0; c0 < channels; c0 += group) {
-    for (int i = 0; i < n_in; ++i) C.src[i].data = cams[i].data + c0;
-    C.dst = out->data + c0;
-    C.ch_count = std::min(group, channels - c0);
-    C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
-    const hipError_t e = lrp::launch_compose_cameras(C, out->lens.type, interpolation, stream);
-    if (e != hipSuccess) return hip_fail(e, "camera compose kernel launch");
-  }
-  return LRP_OK;
+  pack_cameras(C.src, cams, n_in, rotations);
+  return launch_channel_groups(C, out->data, out->channels, post, "camera compose kernel launch",
+                               [&](int) { return lrp::launch_compose_cameras(C, out->lens.type, interpolation, stream); });
 }
 
 static_assert(lrp::kOverlapWords == LRP_OVERLAP_WORDS, "lrp_camstat.h states the table size of include/lrp.h");
@@ -853,13 +896,7 @@ int enqueue_camera_overlap(const lrp_camera *cams, int n_in, const float *rotati
   C.out_lens = pack_lens(out->lens);
   C.n_src = n_in;
   C.lo = lo, C.hi = hi;
-  for (int i = 0; i < n_in; ++i) {
-    lrp::CameraSource &S = C.src[i];
-    pack_camera(S, cams[i]);
-    S.data = cams[i].data;
-    S.has_rot = rotations != nullptr;
-    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
-  }
+  pack_cameras(C.src, cams, n_in, rotations);
   const hipError_t e = lrp::launch_camera_overlap(C, out->lens.type, stream);
   if (e != hipSuccess) return hip_fail(e, "zeroing the overlap table or the camera overlap kernel launch");
   return LRP_OK;
@@ -875,31 +912,224 @@ int enqueue_compose_cameras_gain(const lrp_camera *cams, int n_in, const float *
   lrp::CameraGainParams G;
   std::memset(&G, 0, sizeof(G));
   lrp::CameraParams &C = G.cam;
-  C.out_w = out->width, C.out_h = out->height, C.channels = out->channels;
+  set_camera_fields(C, out->width, out->height, out->channels, n_in, mode, num_samples, post, count, coverage);
   C.out_lens = pack_lens(out->lens);
-  if (post) C.exposure = post->exposure, C.reinhard = post->reinhard;
+  pack_cameras(C.src, cams, n_in, rotations);
+  for (int i = 0; i < n_in; ++i) G.gain[i] = gains[i];
+  return launch_channel_groups(C, out->data, out->channels, post, "camera gain compose kernel launch", [&](int c0) {
+    return c0 == 0 ? lrp::launch_compose_cameras_gain(G, out->lens.type, interpolation, stream)
+                   : lrp::launch_compose_cameras(C, out->lens.type, interpolation, stream);
+  });
+}
+
+static_assert(lrp::kCameraInverseSteps == LRP_CAMERA_INVERSE_STEPS, "lrp_camera_inverse.h takes the step count of include/lrp.h");
+
+// lrp_camera_view_device's checks, in the order include/lrp.h states.
+int validate_camera_view(const lrp_camera *cams, int n_in, const lrp_camera *target, const float *out_data, int channels, int num_samples,
+                         int interpolation, int mode) {
+  int st = check_sources_and_mode(n_in, mode);
+  if (st != LRP_OK) return st;
+  if (!cams || !target || !out_data) return fail(LRP_ERR_NULL, !cams ? "null camera array" : !target ? "null target camera" : "null output data");
+  st = validate_camera(*target, "target: ", std::max(channels, 1), false); // (channels < 1 is the next check's)
+  if (st != LRP_OK) return st;
+  if (channels < 1) return fail(LRP_ERR_CHANNELS, "channels must be >= 1");
+  st = check_three_samplers(interpolation);
+  if (st != LRP_OK) return st;
   for (int i = 0; i < n_in; ++i) {
-    lrp::CameraSource &S = C.src[i];
-    pack_camera(S, cams[i]);
-    S.has_rot = rotations != nullptr;
-    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
-    G.gain[i] = gains[i];
+    st = validate_camera(cams[i], "camera " + std::to_string(i) + ": ", channels, true);
+    if (st != LRP_OK) return st;
   }
-  C.n_src = n_in;
-  C.mode = mode;
-  C.num_samples = num_samples;
+  return check_compose_samples(num_samples);
+}
+
+// One launch of the camera-view kernel per group of 8 channels (lrp_camview.hip), each of which writes the planes; no table, no
+// geometry-cache entry, no allocation.
+int enqueue_camera_view(const lrp_camera *cams, int n_in, const float *rotations, const lrp_camera *target, float *out_data, int channels,
+                        int num_samples, int interpolation, int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, hipStream_t stream) {
+  if (!lrp::launch_camera_view) return fail(LRP_ERR_HIP, "the camera-view kernels (lrp_camview.hip) are not part of this build");
+  lrp::CameraViewParams C;
+  std::memset(&C, 0, sizeof(C));
+  set_camera_fields(C, target->width, target->height, channels, n_in, mode, num_samples, post, count, coverage);
+  pack_camera(C.target, *target);
+  pack_cameras(C.src, cams, n_in, rotations);
+  return launch_channel_groups(C, out_data, channels, post, "camera-view kernel launch",
+                               [&](int) { return lrp::launch_camera_view(C, interpolation, stream); });
+}
+
+static_assert((int)lrp::kPackedF32 == LRP_PIXEL_F32 && (int)lrp::kPackedF16 == LRP_PIXEL_F16 && (int)lrp::kPackedU8 == LRP_PIXEL_U8_GAMMA, "lrp_packed.h numbers pixel formats like include/lrp.h");
+
+bool format_ok(int f) { return f == LRP_PIXEL_F32 || f == LRP_PIXEL_F16 || f == LRP_PIXEL_U8_GAMMA; }
+
+// The packed image of `packed_channels` samples per pixel fits the byte offsets of the packed kernel (32-bit): the size limit of
+// validate() — 2^31 — applied to bytes.  (Dimensions are positive: validate() ran.)
+bool packed_addressable(const lrp_image &im, int format, int packed_channels) {
+  const unsigned long long px = (unsigned long long)im.width * (unsigned long long)im.height; // < 2^62
+  const unsigned long long sample = lrp::pixel_bytes(format, 1);
+  return px <= kMaxImageFloats / sample && (unsigned long long)packed_channels <= kMaxImageFloats / (px * sample);
+}
+
+// What every packed call adds to the checks of its float32 parent ahead of the sizes in bytes, in the order include/lrp.h states:
+// a float32 source (`float32_needs`: the subject and verb of the call's text, `instead`: the calls it names), the formats (has_out
+// false: a call without a packed output), the packed channel counts, C (`who_does`: the entry point and its verb, in front of "at
+// most 4 channels").
+int check_packed_formats(int in_format, int in_pch, bool has_out, int out_format, int out_pch, int channels, const char *float32_needs,
+                         const char *instead, const char *who_does) {
+  if (in_format == LRP_PIXEL_F32) return fail(LRP_ERR_BAD_ARG, std::string(float32_needs) + " no decode: call " + instead);
+  if (!format_ok(in_format) || (has_out && !format_ok(out_format))) return fail(LRP_ERR_BAD_ARG, "unknown pixel format");
+  if (in_pch < 1 || (has_out && out_pch < 1)) return fail(LRP_ERR_BAD_ARG, "packed channel counts must be >= 1");
+  if (channels > lrp::kPackedMaxChannels)
+    return fail(LRP_ERR_CHANNELS, std::string(who_does) + " at most " + std::to_string(lrp::kPackedMaxChannels) + " channels");
+  return LRP_OK;
+}
+
+// lrp_reproject_packed_device's checks, in the order include/lrp.h states.
+int validate_packed(const lrp_image *in, int in_format, int in_pch, const lrp_image *out, int out_format, int out_pch, int interpolation) {
+  int st = validate(in, out, interpolation, true, false);
+  if (st != LRP_OK) return st;
+  st = check_packed_formats(in_format, in_pch, true, out_format, out_pch, in->channels, "a float32 source needs",
+                            "lrp_reproject_device + lrp_encode_pixels_device", "lrp_reproject_packed_device renders");
+  if (st != LRP_OK) return st;
+  if (!packed_addressable(*in, in_format, in_pch) || !packed_addressable(*out, out_format, out_pch))
+    return fail(LRP_ERR_BAD_DIMS, "a packed image of more than 2^31 bytes cannot be addressed (the packed kernel forms 32-bit byte offsets)");
+  return LRP_OK;
+}
+
+// One launch of the packed kernel (lrp_packed.hip).  num_samples == 1: through the geometry cache, under the key
+// enqueue_reproject builds for this geometry — the entry is shared with lrp_reproject_device in both directions.
+int enqueue_packed(const lrp_image *in, int in_format, int in_pch, lrp_image *out, int out_format, int out_pch, unsigned out_fill,
+                   int num_samples, int interpolation, const float *rotation, const lrp_post *post, int device, hipStream_t stream) {
+  if (num_samples <= 0) return LRP_OK; // reference loop body never runs: output untouched
+  if (!lrp::launch_packed) return fail(LRP_ERR_HIP, "the packed-pixel kernels (lrp_packed.hip) are not part of this build");
+  const lrp::KParams K = make_params(in, out, num_samples, rotation, post);
+  lrp::PackedParams P;
+  std::memset(&P, 0, sizeof(P));
+  P.src = in->data, P.dst = out->data;
+  P.in_w = K.in_w, P.in_h = K.in_h, P.out_w = K.out_w, P.out_h = K.out_h;
+  P.channels = K.channels;
+  P.in_channels = in_pch, P.out_channels = out_pch;
+  P.out_format = out_format;
+  P.out_fill = out_fill;
+  P.num_samples = K.num_samples;
+  P.normalize = K.normalize;
+  P.in_lens = K.in_lens, P.out_lens = K.out_lens;
+  std::memcpy(P.rot, K.rot, sizeof(P.rot));
+  P.has_rot = K.has_rot, P.has_post = K.has_post;
+  P.exposure = K.exposure, P.reinhard = K.reinhard;
+  const int ol = out->lens.type, im = in_lens_mode(in->lens);
+  lrp::GeoUse geo;
+  if (num_samples == 1 && knob(kKnobGeoCache) != 0) {
+    lrp::GeoKey key;
+    std::memset(&key, 0, sizeof(key));
+    key.device = device;
+    key.out_type = ol;
+    key.in_mode = im;
+    key.out_w = out->width, key.out_h = out->height, key.in_w = in->width, key.in_h = in->height;
+    key.has_rot = P.has_rot;
+    key.num_samples = num_samples;
+    key.out_lens = lrp::geo_canonical_lens(P.out_lens, out->lens.type), key.in_lens = lrp::geo_canonical_lens(P.in_lens, in->lens.type);
+    if (P.has_rot) std::memcpy(key.rot, P.rot, sizeof(key.rot));
+    lrp::geo_acquire(key, /*want_boxes=*/false, stream, &geo);
+    if (geo.mode == 1 || geo.mode == 2) {
+      P.geo_mode = geo.mode;
+      P.geo_xy = geo.xy;
+    }
+  }
+  const hipError_t e = lrp::launch_packed(P, in_format, ol, im, interpolation, device, stream);
+  lrp::geo_launched(&geo, stream, e == hipSuccess);
+  if (e != hipSuccess) return hip_fail(e, "packed-pixel kernel launch");
+  return LRP_OK;
+}
+
+// lrp_compose_packed_device's checks, in the order include/lrp.h states: those of lrp_compose_device, then those
+// lrp_reproject_packed_device adds to lrp_reproject_device's.
+int validate_compose_packed(const lrp_image *ins, int n_in, int in_format, int in_pch, const lrp_image *out, int out_format, int out_pch,
+                            int interpolation, int mode) {
+  int st = validate_compose(ins, n_in, out, interpolation, mode);
+  if (st != LRP_OK) return st;
+  st = check_packed_formats(in_format, in_pch, true, out_format, out_pch, out->channels, "float32 sources need",
+                            "lrp_compose_device + lrp_encode_pixels_device", "lrp_compose_packed_device composes");
+  if (st != LRP_OK) return st;
+  bool fits = packed_addressable(*out, out_format, out_pch);
+  for (int i = 0; i < n_in; ++i) fits = fits && packed_addressable(ins[i], in_format, in_pch);
+  if (!fits) return fail(LRP_ERR_BAD_DIMS, "a packed image of more than 2^31 bytes cannot be addressed (the packed compose kernel forms 32-bit byte offsets)");
+  return LRP_OK;
+}
+
+// One launch of the packed compose kernel (lrp_compose_packed.hip); no table but the two 8-bit ones, no geometry-cache entry, no
+// allocation.
+int enqueue_compose_packed(const lrp_image *ins, int n_in, int in_format, int in_pch, const float *rotations, const lrp_image *out,
+                           int out_format, int out_pch, unsigned out_fill, int interpolation, int mode, const lrp_post *post, uint8_t *count,
+                           int device, hipStream_t stream) {
+  if (!lrp::launch_compose_packed) return fail(LRP_ERR_HIP, "the packed compose kernels (lrp_compose_packed.hip) are not part of this build");
+  lrp::ComposePackedParams C;
+  std::memset(&C, 0, sizeof(C));
+  pack_ideal_sources(C, ins, n_in, rotations, out, mode, post);
+  C.dst = out->data;
   C.count = count;
-  C.coverage = coverage;
-  const int channels = out->channels, group = lrp::kComposeMaxChannels;
-  for (int c0 = 0; c0 < channels; c0 += group) {
-    for (int i = 0; i < n_in; ++i) C.src[i].data = cams[i].data + c0;
-    C.dst = out->data + c0;
-    C.ch_count = std::min(group, channels - c0);
-    C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
-    const hipError_t e = c0 == 0 ? lrp::launch_compose_cameras_gain(G, out->lens.type, interpolation, stream)
-                                 : lrp::launch_compose_cameras(C, out->lens.type, interpolation, stream);
-    if (e != hipSuccess) return hip_fail(e, "camera gain compose kernel launch");
+  C.in_channels = in_pch, C.out_channels = out_pch;
+  C.out_format = out_format;
+  C.out_fill = out_fill;
+  const hipError_t e = lrp::launch_compose_packed(C, in_format, out->lens.type, in_lens_mode(ins[0].lens), interpolation, device, stream);
+  if (e != hipSuccess) return hip_fail(e, "packed compose kernel launch");
+  return LRP_OK;
+}
+
+// What the packed camera calls add to the checks of their float32 parents, in the order include/lrp.h states:
+// check_packed_formats (who_takes: the entry point and "takes", instead: the calls for float32 frames), then the sizes in bytes.
+// (Dimensions are positive: the parents' checks ran.)
+int validate_cameras_packed(const lrp_camera *cams, int n_in, int in_format, int in_pch, const lrp_image *out, bool has_out, int out_format,
+                            int out_pch, const char *who_takes, const char *instead) {
+  const int st = check_packed_formats(in_format, in_pch, has_out, out_format, out_pch, out->channels, "float32 frames need", instead, who_takes);
+  if (st != LRP_OK) return st;
+  bool fits = !has_out || packed_addressable(*out, out_format, out_pch);
+  for (int i = 0; i < n_in; ++i) {
+    lrp_image frame;
+    std::memset(&frame, 0, sizeof(frame));
+    frame.width = cams[i].width, frame.height = cams[i].height;
+    fits = fits && packed_addressable(frame, in_format, in_pch);
   }
+  if (!fits) return fail(LRP_ERR_BAD_DIMS, "a packed frame or output of more than 2^31 bytes cannot be addressed (the packed camera kernels form 32-bit byte offsets)");
+  return LRP_OK;
+}
+
+// One launch of the packed camera compose kernel (lrp_camera_packed.hip); no table but the two 8-bit ones, no geometry-cache
+// entry, no allocation.  gains == nullptr: a gain of 1.0f per camera.
+int enqueue_compose_cameras_packed(const lrp_camera *cams, int n_in, int in_format, int in_pch, const float *rotations, const float *gains,
+                                   const lrp_image *out, int out_format, int out_pch, unsigned out_fill, int num_samples, int interpolation,
+                                   int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, int device, hipStream_t stream) {
+  if (!lrp::launch_compose_cameras_packed) return fail(LRP_ERR_HIP, "the packed camera compose kernels (lrp_camera_packed.hip) are not part of this build");
+  lrp::CameraPackedParams C;
+  std::memset(&C, 0, sizeof(C));
+  set_camera_fields(C, out->width, out->height, out->channels, n_in, mode, num_samples, post, count, coverage);
+  C.dst = out->data;
+  C.in_channels = in_pch, C.out_channels = out_pch;
+  C.out_format = out_format;
+  C.out_fill = out_fill;
+  C.out_lens = pack_lens(out->lens);
+  C.has_post = post != nullptr;
+  pack_cameras(C.src, cams, n_in, rotations);
+  for (int i = 0; i < n_in; ++i) C.gain[i] = gains ? gains[i] : 1.0f;
+  const hipError_t e = lrp::launch_compose_cameras_packed(C, in_format, out->lens.type, interpolation, device, stream);
+  if (e != hipSuccess) return hip_fail(e, "packed camera compose kernel launch");
+  return LRP_OK;
+}
+
+// The launcher (lrp_camstat_packed.hip) zeroes the table on `stream` ahead of the one launch of the packed overlap kernel, which
+// adds into it; no allocation, no geometry-cache entry.
+int enqueue_camera_overlap_packed(const lrp_camera *cams, int n_in, int in_format, int in_pch, const float *rotations, const lrp_image *out,
+                                  float lo, float hi, uint64_t *stats, int device, hipStream_t stream) {
+  if (!lrp::launch_camera_overlap_packed) return fail(LRP_ERR_HIP, "the packed camera overlap kernels (lrp_camstat_packed.hip) are not part of this build");
+  lrp::CameraStatPackedParams C;
+  std::memset(&C, 0, sizeof(C));
+  C.stats = reinterpret_cast<unsigned long long *>(stats);
+  C.out_w = out->width, C.out_h = out->height, C.channels = out->channels;
+  C.in_channels = in_pch;
+  C.out_lens = pack_lens(out->lens);
+  C.n_src = n_in;
+  C.lo = lo, C.hi = hi;
+  pack_cameras(C.src, cams, n_in, rotations);
+  const hipError_t e = lrp::launch_camera_overlap_packed(C, in_format, out->lens.type, device, stream);
+  if (e != hipSuccess) return hip_fail(e, "zeroing the overlap table or the packed camera overlap kernel launch");
   return LRP_OK;
 }
 
@@ -908,12 +1138,12 @@ static_assert(lrp::kMultibandMaxBands == LRP_MULTIBAND_MAX_BANDS && lrp::kMultib
 // Items 1 to 6 of lrp_compose_cameras_multiband_device, in the order include/lrp.h states; its packed twin runs them first.
 int validate_multiband(const lrp_camera *cams, int n_in, const float *gains, const lrp_image *out, int interpolation, int num_bands,
                        const void *scratch, size_t scratch_bytes) {
-  const int st = validate_cameras_and_output(cams, n_in, out, interpolation, LRP_COMPOSE_FIRST, true, false, nullptr);
+  int st = validate_cameras_and_output(cams, n_in, out, interpolation, LRP_COMPOSE_FIRST, true, false, nullptr);
   if (st != LRP_OK) return st;
-  if (gains)
-    for (int i = 0; i < n_in; ++i)
-      if (!std::isfinite(gains[i]) || gains[i] < 0.0f)
-        return fail(LRP_ERR_BAD_ARG, "camera " + std::to_string(i) + ": gain must be finite and not negative");
+  if (gains) {
+    st = check_gains(gains, n_in);
+    if (st != LRP_OK) return st;
+  }
   if (out->channels > lrp::kMultibandMaxChannels) return fail(LRP_ERR_CHANNELS, "out->channels of a multi-band call must be 1 .. 4");
   if (num_bands < 0 || num_bands > LRP_MULTIBAND_MAX_BANDS) return fail(LRP_ERR_BAD_ARG, "num_bands must be 0 .. " + std::to_string(LRP_MULTIBAND_MAX_BANDS));
   if (!scratch) return fail(LRP_ERR_NULL, "null scratch");
@@ -939,9 +1169,6 @@ struct MultibandPacked {
   unsigned out_fill;
   int device;
 };
-int enqueue_compose_cameras_packed(const lrp_camera *cams, int n_in, int in_format, int in_pch, const float *rotations, const float *gains,
-                                   const lrp_image *out, int out_format, int out_pch, unsigned out_fill, int num_samples, int interpolation,
-                                   int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, int device, hipStream_t stream);
 int enqueue_multiband(const lrp_camera *cams, int n_in, const float *rotations, const float *gains, const lrp_image *out, int interpolation,
                       int num_bands, const lrp_post *post, uint8_t *count, uint8_t *label, void *scratch, const MultibandPacked *packed,
                       hipStream_t stream) {
@@ -963,12 +1190,7 @@ int enqueue_multiband(const lrp_camera *cams, int n_in, const float *rotations, 
   LP.out_w = out->width, LP.out_h = out->height;
   LP.n_src = n_in;
   LP.out_lens = pack_lens(out->lens);
-  for (int i = 0; i < n_in; ++i) {
-    lrp::CameraSource &S = LP.src[i];
-    pack_camera(S, cams[i]);
-    S.has_rot = rotations != nullptr;
-    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
-  }
+  pack_cameras(LP.src, cams, n_in, rotations); // (the data pointers ride along: the label kernel reads the geometry only)
   hipError_t e = lrp::launch_multiband_label(LP, out->lens.type, stream);
   if (e != hipSuccess) return hip_fail(e, "multi-band label kernel launch");
 
@@ -1039,268 +1261,6 @@ int enqueue_multiband(const lrp_camera *cams, int n_in, const float *rotations, 
     e = lrp::launch_mb_collapse_packed(K, C, packed->device, stream);
     if (e != hipSuccess) return hip_fail(e, "packed multi-band collapse kernel launch");
   }
-  return LRP_OK;
-}
-
-static_assert(lrp::kCameraInverseSteps == LRP_CAMERA_INVERSE_STEPS, "lrp_camera_inverse.h takes the step count of include/lrp.h");
-
-// lrp_camera_view_device's checks, in the order include/lrp.h states.
-int validate_camera_view(const lrp_camera *cams, int n_in, const lrp_camera *target, const float *out_data, int channels, int num_samples,
-                         int interpolation, int mode) {
-  if (n_in < 1 || n_in > LRP_COMPOSE_MAX_SOURCES)
-    return fail(LRP_ERR_BAD_ARG, "n_in of a compose call must be 1 .. " + std::to_string(LRP_COMPOSE_MAX_SOURCES));
-  if (mode != LRP_COMPOSE_FIRST && mode != LRP_COMPOSE_MEAN && mode != LRP_COMPOSE_FEATHER) return fail(LRP_ERR_BAD_ARG, "unknown compose mode");
-  if (!cams || !target || !out_data) return fail(LRP_ERR_NULL, !cams ? "null camera array" : !target ? "null target camera" : "null output data");
-  int st = validate_camera(*target, "target: ", std::max(channels, 1), false); // (channels < 1 is the next check's)
-  if (st != LRP_OK) return st;
-  if (channels < 1) return fail(LRP_ERR_CHANNELS, "channels must be >= 1");
-  if (interpolation != LRP_NEAREST && interpolation != LRP_BILINEAR && interpolation != LRP_BICUBIC)
-    return fail(LRP_ERR_INTERPOLATION, "Interpolation method not supported.");
-  for (int i = 0; i < n_in; ++i) {
-    st = validate_camera(cams[i], "camera " + std::to_string(i) + ": ", channels, true);
-    if (st != LRP_OK) return st;
-  }
-  if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
-    return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
-  return LRP_OK;
-}
-
-// One launch of the camera-view kernel per group of 8 channels (lrp_camview.hip), each of which writes the planes; no table, no
-// geometry-cache entry, no allocation.
-int enqueue_camera_view(const lrp_camera *cams, int n_in, const float *rotations, const lrp_camera *target, float *out_data, int channels,
-                        int num_samples, int interpolation, int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, hipStream_t stream) {
-  if (!lrp::launch_camera_view) return fail(LRP_ERR_HIP, "the camera-view kernels (lrp_camview.hip) are not part of this build");
-  lrp::CameraViewParams C;
-  std::memset(&C, 0, sizeof(C));
-  C.out_w = target->width, C.out_h = target->height, C.channels = channels;
-  pack_camera(C.target, *target);
-  if (post) C.exposure = post->exposure, C.reinhard = post->reinhard;
-  for (int i = 0; i < n_in; ++i) {
-    lrp::CameraSource &S = C.src[i];
-    pack_camera(S, cams[i]);
-    S.has_rot = rotations != nullptr;
-    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
-  }
-  C.n_src = n_in;
-  C.mode = mode;
-  C.num_samples = num_samples;
-  C.count = count;
-  C.coverage = coverage;
-  const int group = lrp::kComposeMaxChannels;
-  for (int c0 = 0; c0 < channels; c0 += group) {
-    for (int i = 0; i < n_in; ++i) C.src[i].data = cams[i].data + c0;
-    C.dst = out_data + c0;
-    C.ch_count = std::min(group, channels - c0);
-    C.has_post = post != nullptr && c0 == 0; // (the tonemap touches channels 0-2)
-    const hipError_t e = lrp::launch_camera_view(C, interpolation, stream);
-    if (e != hipSuccess) return hip_fail(e, "camera-view kernel launch");
-  }
-  return LRP_OK;
-}
-
-static_assert((int)lrp::kPackedF32 == LRP_PIXEL_F32 && (int)lrp::kPackedF16 == LRP_PIXEL_F16 && (int)lrp::kPackedU8 == LRP_PIXEL_U8_GAMMA, "lrp_packed.h numbers pixel formats like include/lrp.h");
-
-bool format_ok(int f) { return f == LRP_PIXEL_F32 || f == LRP_PIXEL_F16 || f == LRP_PIXEL_U8_GAMMA; }
-
-// The packed image of `packed_channels` samples per pixel fits the byte offsets of the packed kernel (32-bit): the size limit of
-// validate() — 2^31 — applied to bytes.  (Dimensions are positive: validate() ran.)
-bool packed_addressable(const lrp_image &im, int format, int packed_channels) {
-  const unsigned long long px = (unsigned long long)im.width * (unsigned long long)im.height; // < 2^62
-  const unsigned long long sample = lrp::pixel_bytes(format, 1);
-  return px <= kMaxImageFloats / sample && (unsigned long long)packed_channels <= kMaxImageFloats / (px * sample);
-}
-
-// lrp_reproject_packed_device's checks, in the order include/lrp.h states.
-int validate_packed(const lrp_image *in, int in_format, int in_pch, const lrp_image *out, int out_format, int out_pch, int interpolation) {
-  const int st = validate(in, out, interpolation, true, false);
-  if (st != LRP_OK) return st;
-  if (in_format == LRP_PIXEL_F32)
-    return fail(LRP_ERR_BAD_ARG, "a float32 source needs no decode: call lrp_reproject_device + lrp_encode_pixels_device");
-  if (!format_ok(in_format) || !format_ok(out_format)) return fail(LRP_ERR_BAD_ARG, "unknown pixel format");
-  if (in_pch < 1 || out_pch < 1) return fail(LRP_ERR_BAD_ARG, "packed channel counts must be >= 1");
-  if (in->channels > lrp::kPackedMaxChannels)
-    return fail(LRP_ERR_CHANNELS, "lrp_reproject_packed_device renders at most " + std::to_string(lrp::kPackedMaxChannels) + " channels");
-  if (!packed_addressable(*in, in_format, in_pch) || !packed_addressable(*out, out_format, out_pch))
-    return fail(LRP_ERR_BAD_DIMS, "a packed image of more than 2^31 bytes cannot be addressed (the packed kernel forms 32-bit byte offsets)");
-  return LRP_OK;
-}
-
-// One launch of the packed kernel (lrp_packed.hip).  num_samples == 1: through the geometry cache, under the key
-// enqueue_reproject builds for this geometry — the entry is shared with lrp_reproject_device in both directions.
-int enqueue_packed(const lrp_image *in, int in_format, int in_pch, lrp_image *out, int out_format, int out_pch, unsigned out_fill,
-                   int num_samples, int interpolation, const float *rotation, const lrp_post *post, int device, hipStream_t stream) {
-  if (num_samples <= 0) return LRP_OK; // reference loop body never runs: output untouched
-  if (!lrp::launch_packed) return fail(LRP_ERR_HIP, "the packed-pixel kernels (lrp_packed.hip) are not part of this build");
-  const lrp::KParams K = make_params(in, out, num_samples, rotation, post);
-  lrp::PackedParams P;
-  std::memset(&P, 0, sizeof(P));
-  P.src = in->data, P.dst = out->data;
-  P.in_w = K.in_w, P.in_h = K.in_h, P.out_w = K.out_w, P.out_h = K.out_h;
-  P.channels = K.channels;
-  P.in_channels = in_pch, P.out_channels = out_pch;
-  P.out_format = out_format;
-  P.out_fill = out_fill;
-  P.num_samples = K.num_samples;
-  P.normalize = K.normalize;
-  P.in_lens = K.in_lens, P.out_lens = K.out_lens;
-  std::memcpy(P.rot, K.rot, sizeof(P.rot));
-  P.has_rot = K.has_rot, P.has_post = K.has_post;
-  P.exposure = K.exposure, P.reinhard = K.reinhard;
-  const int ol = out->lens.type, im = in_lens_mode(in->lens);
-  lrp::GeoUse geo;
-  if (num_samples == 1 && knob(kKnobGeoCache) != 0) {
-    lrp::GeoKey key;
-    std::memset(&key, 0, sizeof(key));
-    key.device = device;
-    key.out_type = ol;
-    key.in_mode = im;
-    key.out_w = out->width, key.out_h = out->height, key.in_w = in->width, key.in_h = in->height;
-    key.has_rot = P.has_rot;
-    key.num_samples = num_samples;
-    key.out_lens = lrp::geo_canonical_lens(P.out_lens, out->lens.type), key.in_lens = lrp::geo_canonical_lens(P.in_lens, in->lens.type);
-    if (P.has_rot) std::memcpy(key.rot, P.rot, sizeof(key.rot));
-    lrp::geo_acquire(key, /*want_boxes=*/false, stream, &geo);
-    if (geo.mode == 1 || geo.mode == 2) {
-      P.geo_mode = geo.mode;
-      P.geo_xy = geo.xy;
-    }
-  }
-  const hipError_t e = lrp::launch_packed(P, in_format, ol, im, interpolation, device, stream);
-  lrp::geo_launched(&geo, stream, e == hipSuccess);
-  if (e != hipSuccess) return hip_fail(e, "packed-pixel kernel launch");
-  return LRP_OK;
-}
-
-// lrp_compose_packed_device's checks, in the order include/lrp.h states: those of lrp_compose_device, then those
-// lrp_reproject_packed_device adds to lrp_reproject_device's.
-int validate_compose_packed(const lrp_image *ins, int n_in, int in_format, int in_pch, const lrp_image *out, int out_format, int out_pch,
-                            int interpolation, int mode) {
-  const int st = validate_compose(ins, n_in, out, interpolation, mode);
-  if (st != LRP_OK) return st;
-  if (in_format == LRP_PIXEL_F32)
-    return fail(LRP_ERR_BAD_ARG, "float32 sources need no decode: call lrp_compose_device + lrp_encode_pixels_device");
-  if (!format_ok(in_format) || !format_ok(out_format)) return fail(LRP_ERR_BAD_ARG, "unknown pixel format");
-  if (in_pch < 1 || out_pch < 1) return fail(LRP_ERR_BAD_ARG, "packed channel counts must be >= 1");
-  if (out->channels > lrp::kPackedMaxChannels)
-    return fail(LRP_ERR_CHANNELS, "lrp_compose_packed_device composes at most " + std::to_string(lrp::kPackedMaxChannels) + " channels");
-  bool fits = packed_addressable(*out, out_format, out_pch);
-  for (int i = 0; i < n_in; ++i) fits = fits && packed_addressable(ins[i], in_format, in_pch);
-  if (!fits) return fail(LRP_ERR_BAD_DIMS, "a packed image of more than 2^31 bytes cannot be addressed (the packed compose kernel forms 32-bit byte offsets)");
-  return LRP_OK;
-}
-
-// One launch of the packed compose kernel (lrp_compose_packed.hip); no table but the two 8-bit ones, no geometry-cache entry, no
-// allocation.
-int enqueue_compose_packed(const lrp_image *ins, int n_in, int in_format, int in_pch, const float *rotations, const lrp_image *out,
-                           int out_format, int out_pch, unsigned out_fill, int interpolation, int mode, const lrp_post *post, uint8_t *count,
-                           int device, hipStream_t stream) {
-  if (!lrp::launch_compose_packed) return fail(LRP_ERR_HIP, "the packed compose kernels (lrp_compose_packed.hip) are not part of this build");
-  lrp::ComposePackedParams C;
-  std::memset(&C, 0, sizeof(C));
-  for (int i = 0; i < n_in; ++i) { // the per-source values as make_params() packs them for a reprojection of source i
-    const lrp::KParams P = make_params(ins + i, out, 1, rotations ? rotations + 9 * i : nullptr, post);
-    if (i == 0) {
-      C.out_w = P.out_w, C.out_h = P.out_h, C.channels = P.channels;
-      C.out_lens = P.out_lens;
-      C.has_post = P.has_post;
-      C.exposure = P.exposure, C.reinhard = P.reinhard;
-    }
-    lrp::ComposePackedSource &S = C.src[i];
-    S.data = ins[i].data;
-    S.in_w = P.in_w, S.in_h = P.in_h;
-    S.lens = P.in_lens;
-    S.has_rot = P.has_rot;
-    std::memcpy(S.rot, P.rot, sizeof(S.rot));
-  }
-  C.dst = out->data;
-  C.count = count;
-  C.in_channels = in_pch, C.out_channels = out_pch;
-  C.out_format = out_format;
-  C.out_fill = out_fill;
-  C.n_src = n_in;
-  C.mode = mode;
-  const hipError_t e = lrp::launch_compose_packed(C, in_format, out->lens.type, in_lens_mode(ins[0].lens), interpolation, device, stream);
-  if (e != hipSuccess) return hip_fail(e, "packed compose kernel launch");
-  return LRP_OK;
-}
-
-// What the packed camera calls add to the checks of their float32 parents, in the order include/lrp.h states: the formats
-// (has_out false: a call without a packed output), the packed channel counts, C, the sizes in bytes.  (Dimensions are positive:
-// the parents' checks ran.)
-int validate_cameras_packed(const lrp_camera *cams, int n_in, int in_format, int in_pch, const lrp_image *out, bool has_out, int out_format,
-                            int out_pch, const char *who, const char *instead) {
-  if (in_format == LRP_PIXEL_F32) return fail(LRP_ERR_BAD_ARG, std::string("float32 frames need no decode: call ") + instead);
-  if (!format_ok(in_format) || (has_out && !format_ok(out_format))) return fail(LRP_ERR_BAD_ARG, "unknown pixel format");
-  if (in_pch < 1 || (has_out && out_pch < 1)) return fail(LRP_ERR_BAD_ARG, "packed channel counts must be >= 1");
-  if (out->channels > lrp::kPackedMaxChannels)
-    return fail(LRP_ERR_CHANNELS, std::string(who) + " takes at most " + std::to_string(lrp::kPackedMaxChannels) + " channels");
-  bool fits = !has_out || packed_addressable(*out, out_format, out_pch);
-  for (int i = 0; i < n_in; ++i) {
-    lrp_image frame;
-    std::memset(&frame, 0, sizeof(frame));
-    frame.width = cams[i].width, frame.height = cams[i].height;
-    fits = fits && packed_addressable(frame, in_format, in_pch);
-  }
-  if (!fits) return fail(LRP_ERR_BAD_DIMS, "a packed frame or output of more than 2^31 bytes cannot be addressed (the packed camera kernels form 32-bit byte offsets)");
-  return LRP_OK;
-}
-
-// One launch of the packed camera compose kernel (lrp_camera_packed.hip); no table but the two 8-bit ones, no geometry-cache
-// entry, no allocation.  gains == nullptr: a gain of 1.0f per camera.
-int enqueue_compose_cameras_packed(const lrp_camera *cams, int n_in, int in_format, int in_pch, const float *rotations, const float *gains,
-                                   const lrp_image *out, int out_format, int out_pch, unsigned out_fill, int num_samples, int interpolation,
-                                   int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, int device, hipStream_t stream) {
-  if (!lrp::launch_compose_cameras_packed) return fail(LRP_ERR_HIP, "the packed camera compose kernels (lrp_camera_packed.hip) are not part of this build");
-  lrp::CameraPackedParams C;
-  std::memset(&C, 0, sizeof(C));
-  C.dst = out->data;
-  C.count = count;
-  C.coverage = coverage;
-  C.out_w = out->width, C.out_h = out->height, C.channels = out->channels;
-  C.in_channels = in_pch, C.out_channels = out_pch;
-  C.out_format = out_format;
-  C.out_fill = out_fill;
-  C.out_lens = pack_lens(out->lens);
-  C.has_post = post != nullptr;
-  if (post) C.exposure = post->exposure, C.reinhard = post->reinhard;
-  for (int i = 0; i < n_in; ++i) {
-    lrp::CameraSource &S = C.src[i];
-    pack_camera(S, cams[i]);
-    S.data = cams[i].data;
-    S.has_rot = rotations != nullptr;
-    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
-    C.gain[i] = gains ? gains[i] : 1.0f;
-  }
-  C.n_src = n_in;
-  C.mode = mode;
-  C.num_samples = num_samples;
-  const hipError_t e = lrp::launch_compose_cameras_packed(C, in_format, out->lens.type, interpolation, device, stream);
-  if (e != hipSuccess) return hip_fail(e, "packed camera compose kernel launch");
-  return LRP_OK;
-}
-
-// The launcher (lrp_camstat_packed.hip) zeroes the table on `stream` ahead of the one launch of the packed overlap kernel, which
-// adds into it; no allocation, no geometry-cache entry.
-int enqueue_camera_overlap_packed(const lrp_camera *cams, int n_in, int in_format, int in_pch, const float *rotations, const lrp_image *out,
-                                  float lo, float hi, uint64_t *stats, int device, hipStream_t stream) {
-  if (!lrp::launch_camera_overlap_packed) return fail(LRP_ERR_HIP, "the packed camera overlap kernels (lrp_camstat_packed.hip) are not part of this build");
-  lrp::CameraStatPackedParams C;
-  std::memset(&C, 0, sizeof(C));
-  C.stats = reinterpret_cast<unsigned long long *>(stats);
-  C.out_w = out->width, C.out_h = out->height, C.channels = out->channels;
-  C.in_channels = in_pch;
-  C.out_lens = pack_lens(out->lens);
-  C.n_src = n_in;
-  C.lo = lo, C.hi = hi;
-  for (int i = 0; i < n_in; ++i) {
-    lrp::CameraSource &S = C.src[i];
-    pack_camera(S, cams[i]);
-    S.data = cams[i].data;
-    S.has_rot = rotations != nullptr;
-    if (rotations) std::memcpy(S.rot, rotations + 9 * i, sizeof(S.rot));
-  }
-  const hipError_t e = lrp::launch_camera_overlap_packed(C, in_format, out->lens.type, device, stream);
-  if (e != hipSuccess) return hip_fail(e, "zeroing the overlap table or the packed camera overlap kernel launch");
   return LRP_OK;
 }
 
@@ -1485,8 +1445,8 @@ int lrp_compose_ss_device(const lrp_image *ins, int n_in, const float *rotations
                           int mode, const lrp_post *post, uint8_t *count, uint8_t *coverage, int device, void *stream) {
   int st = validate_compose(ins, n_in, out, interpolation, mode);
   if (st != LRP_OK) return st;
-  if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
-    return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
+  st = check_compose_samples(num_samples);
+  if (st != LRP_OK) return st;
   st = select_device(device);
   if (st != LRP_OK) return st;
   return enqueue_compose_ss(ins, n_in, rotations, out, num_samples, interpolation, mode, post, count, coverage, (hipStream_t)stream);
@@ -1506,9 +1466,8 @@ int lrp_camera_overlap_device(const lrp_camera *cams, int n_in, const float *rot
   // (no mode and a fixed sampler: items 1 and 4 see values that pass)
   int st = validate_cameras_and_output(cams, n_in, out, LRP_BILINEAR, LRP_COMPOSE_FIRST, false, false, nullptr);
   if (st != LRP_OK) return st;
-  if (!stats) return fail(LRP_ERR_NULL, "null stats");
-  if (!std::isfinite(lo) || !std::isfinite(hi) || !(0.0f <= lo && lo <= hi && hi <= 32768.0f))
-    return fail(LRP_ERR_BAD_ARG, "lo and hi of an overlap call must be finite with 0 <= lo <= hi <= 32768");
+  st = check_overlap(stats, lo, hi);
+  if (st != LRP_OK) return st;
   st = select_device(device);
   if (st != LRP_OK) return st;
   return enqueue_camera_overlap(cams, n_in, rotations, out, lo, hi, stats, (hipStream_t)stream);
@@ -1575,11 +1534,10 @@ int lrp_compose_cameras_gain_device(const lrp_camera *cams, int n_in, const floa
                                     int device, void *stream) {
   int st = validate_cameras_and_output(cams, n_in, out, interpolation, mode, true, true, gains);
   if (st != LRP_OK) return st;
-  for (int i = 0; i < n_in; ++i)
-    if (!std::isfinite(gains[i]) || gains[i] < 0.0f)
-      return fail(LRP_ERR_BAD_ARG, "camera " + std::to_string(i) + ": gain must be finite and not negative");
-  if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
-    return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
+  st = check_gains(gains, n_in);
+  if (st != LRP_OK) return st;
+  st = check_compose_samples(num_samples);
+  if (st != LRP_OK) return st;
   st = select_device(device);
   if (st != LRP_OK) return st;
   return enqueue_compose_cameras_gain(cams, n_in, rotations, gains, out, num_samples, interpolation, mode, post, count, coverage,
@@ -1709,13 +1667,13 @@ int lrp_compose_cameras_packed_device(const lrp_camera *cams, int n_in, int in_f
                                       int device, void *stream) {
   int st = validate_cameras_and_output(cams, n_in, out, interpolation, mode, true, false, nullptr);
   if (st != LRP_OK) return st;
-  if (gains)
-    for (int i = 0; i < n_in; ++i)
-      if (!std::isfinite(gains[i]) || gains[i] < 0.0f)
-        return fail(LRP_ERR_BAD_ARG, "camera " + std::to_string(i) + ": gain must be finite and not negative");
-  if (num_samples < 1 || num_samples > lrp::kComposeSsMaxSamples)
-    return fail(LRP_ERR_BAD_ARG, "num_samples of a compose call must be 1 .. " + std::to_string(lrp::kComposeSsMaxSamples));
-  st = validate_cameras_packed(cams, n_in, in_format, in_packed_channels, out, true, out_format, out_packed_channels, "lrp_compose_cameras_packed_device",
+  if (gains) {
+    st = check_gains(gains, n_in);
+    if (st != LRP_OK) return st;
+  }
+  st = check_compose_samples(num_samples);
+  if (st != LRP_OK) return st;
+  st = validate_cameras_packed(cams, n_in, in_format, in_packed_channels, out, true, out_format, out_packed_channels, "lrp_compose_cameras_packed_device takes",
                                "lrp_compose_cameras_device or lrp_compose_cameras_gain_device, then lrp_encode_pixels_device");
   if (st != LRP_OK) return st;
   st = select_device(device);
@@ -1732,7 +1690,7 @@ int lrp_compose_cameras_multiband_packed_device(const lrp_camera *cams, int n_in
   if (st != LRP_OK) return st;
   // (C <= 4 has passed: the packed calls' own channel item cannot fire)
   st = validate_cameras_packed(cams, n_in, in_format, in_packed_channels, out, true, out_format, out_packed_channels,
-                               "lrp_compose_cameras_multiband_packed_device", "lrp_compose_cameras_multiband_device, then lrp_encode_pixels_device");
+                               "lrp_compose_cameras_multiband_packed_device takes", "lrp_compose_cameras_multiband_device, then lrp_encode_pixels_device");
   if (st != LRP_OK) return st;
   // a camera's level-0 layer is a float32 image of C samples per pixel in the scratch, written by the packed camera kernel
   if (!packed_addressable(*out, LRP_PIXEL_F32, out->channels))
@@ -1749,10 +1707,9 @@ int lrp_camera_overlap_packed_device(const lrp_camera *cams, int n_in, int in_fo
   // (no mode and a fixed sampler: items 1 and 4 see values that pass)
   int st = validate_cameras_and_output(cams, n_in, out, LRP_BILINEAR, LRP_COMPOSE_FIRST, false, false, nullptr);
   if (st != LRP_OK) return st;
-  if (!stats) return fail(LRP_ERR_NULL, "null stats");
-  if (!std::isfinite(lo) || !std::isfinite(hi) || !(0.0f <= lo && lo <= hi && hi <= 32768.0f))
-    return fail(LRP_ERR_BAD_ARG, "lo and hi of an overlap call must be finite with 0 <= lo <= hi <= 32768");
-  st = validate_cameras_packed(cams, n_in, in_format, in_packed_channels, out, false, 0, 0, "lrp_camera_overlap_packed_device", "lrp_camera_overlap_device");
+  st = check_overlap(stats, lo, hi);
+  if (st != LRP_OK) return st;
+  st = validate_cameras_packed(cams, n_in, in_format, in_packed_channels, out, false, 0, 0, "lrp_camera_overlap_packed_device takes", "lrp_camera_overlap_device");
   if (st != LRP_OK) return st;
   st = select_device(device);
   if (st != LRP_OK) return st;
