@@ -1,23 +1,20 @@
 // lrp_camera.hip — frames of calibrated cameras composed into one output with n x n sub-samples per pixel by one launch
 // (include/lrp.h "compose, calibrated cameras"): the launcher lrp_capi.cpp calls, and the
 // nearest-neighbour instantiations of compose_cam_kernel (lrp_camera_kernel.h).  The bilinear and bicubic ones are
-// lrp_camera_bl.hip and lrp_camera_bc.hip.
+// units of lrp_camera_unit.hip (units.list).
 #include <hip/hip_runtime.h>
 
 #include "lrp_camera_kernel.h"
 
 namespace lrp {
 
-hipError_t launch_compose_cameras_bilinear(const CameraParams &P, int out_lens, hipStream_t stream);
-hipError_t launch_compose_cameras_bicubic(const CameraParams &P, int out_lens, hipStream_t stream);
-
 // P: everything but the tiling.  interpolation: 0 nearest, 1 bilinear, 2 bicubic (include/lrp.h lrp_interpolation).
 hipError_t launch_compose_cameras(const CameraParams &P, int out_lens, int interpolation, hipStream_t stream) {
   if (P.n_src < 1 || P.n_src > kComposeMaxSources || P.ch_count < 1 || P.ch_count > kComposeMaxChannels) return hipErrorInvalidValue;
   if (P.num_samples < 1 || P.num_samples > kComposeSsMaxSamples) return hipErrorInvalidValue;
   if (interpolation == 0) return launch_compose_cameras_interp<0>(P, out_lens, stream);
-  if (interpolation == 1) return launch_compose_cameras_bilinear(P, out_lens, stream);
-  if (interpolation == 2) return launch_compose_cameras_bicubic(P, out_lens, stream);
+  if (interpolation == 1) return launch_compose_cameras_unit<1>(P, out_lens, stream);
+  if (interpolation == 2) return launch_compose_cameras_unit<2>(P, out_lens, stream);
   return hipErrorInvalidValue;
 }
 

@@ -1,7 +1,7 @@
 // lrp_camera_kernel.h — the calibrated-camera compose kernel (include/lrp.h "compose, calibrated cameras", DESIGN.md section
 // 17): several frames of calibrated cameras — fx, fy, cx, cy in pixels plus Brown-Conrady or Kannala-Brandt coefficients —
-// into one output with n x n sub-samples per pixel, one launch.  Included by one .hip unit per interpolation (lrp_camera.hip,
-// lrp_camera_bl.hip, lrp_camera_bc.hip) so that the three instantiation sets compile in parallel.
+// into one output with n x n sub-samples per pixel, one launch.  Included by one unit per interpolation (lrp_camera.hip;
+// lrp_camera_unit.hip twice, units.list) so that the three instantiation sets compile in parallel.
 //
 // Per output pixel: compose_ss_pixel (lrp_compose_pixel.h), the supersampled body, with CameraSources below in place of the
 // sources of an ideal lens: camera_project, the closed-form polynomial from ray to source pixel, its `imaged` test and the box
@@ -83,4 +83,6 @@ template <int Interp> hipError_t launch_compose_cameras_interp(CameraParams P, i
   return launch_compose_tiles(camera_kernel<Interp>(out_lens), P, P, stream);
 }
 
+// ... as a bilinear / bicubic unit of units.list compiles it: defined and instantiated by lrp_camera_unit.hip, declared only for the launcher.
+template <int Interp> hipError_t launch_compose_cameras_unit(const CameraParams &P, int out_lens, hipStream_t stream);
 } // namespace lrp

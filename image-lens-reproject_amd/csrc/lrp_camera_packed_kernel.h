@@ -1,8 +1,8 @@
 // lrp_camera_packed_kernel.h — the packed camera compose kernel (include/lrp.h "calibrated cameras, packed pixels", DESIGN.md
 // section 21): several calibrated cameras' frames of 8-bit or binary16 samples composed, with n x n sub-samples per pixel and one
-// gain per camera, into one output of 8-bit, binary16 or float samples by one launch.  Included by one .hip unit per
-// interpolation (lrp_camera_packed.hip, lrp_camera_packed_bl.hip) and, for the bicubic sampler, one per source format
-// (lrp_camera_packed_bc.hip, lrp_camera_packed_bc_f16.hip), so that the instantiation sets compile in parallel.
+// gain per camera, into one output of 8-bit, binary16 or float samples by one launch.  Included by one unit per
+// interpolation (lrp_camera_packed.hip; lrp_camera_packed_unit.hip, units.list) and, for the bicubic sampler, one per source
+// format, so that the instantiation sets compile in parallel.
 //
 // The bytes are those of lrp_decode_pixels_device per camera -> lrp_compose_cameras_gain_device -> lrp_encode_pixels_device with
 // float32 staging images of C channels in between.  It is compose_ss_pixel's body (lrp_compose_pixel.h) as camgain_kernel
@@ -172,7 +172,7 @@ template <int Interp, int CH, int Fmt> CameraPackedKernelFn camera_packed_kernel
   return table[out_lens];
 }
 
-// One source format's kernels: the unit of the split of the bicubic instantiations (lrp_camera_packed_bc*.hip).
+// One source format's kernels: the unit of the split of the bicubic instantiations (units.list, lrp_camera_packed_bc*.o).
 // P: as launch_compose_cameras_packed (lrp_camera_packed.hip) completed it.
 template <int Interp, int Fmt> hipError_t launch_camera_packed_fmt(const CameraPackedParams &P, int out_lens, hipStream_t stream) {
   if (P.tiles_x <= 0 || P.tiles_y <= 0) return hipSuccess;
@@ -188,4 +188,7 @@ template <int Interp> hipError_t launch_camera_packed_interp(const CameraPackedP
   return launch_camera_packed_fmt<Interp, kPackedF16>(P, out_lens, stream);
 }
 
+// launch_camera_packed_fmt as a bilinear / bicubic unit of units.list compiles it: defined and instantiated by
+// lrp_camera_packed_unit.hip, declared only for the launcher.
+template <int Interp, int Fmt> hipError_t launch_camera_packed_unit(const CameraPackedParams &P, int out_lens, hipStream_t stream);
 } // namespace lrp

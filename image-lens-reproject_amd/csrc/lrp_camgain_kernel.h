@@ -1,6 +1,6 @@
 // lrp_camgain_kernel.h — the calibrated-camera compose kernel with one gain per camera (include/lrp.h "exposure matching across
-// a camera rig").  Included by one .hip unit per interpolation (lrp_camgain.hip, lrp_camgain_bl.hip,
-// lrp_camgain_bc.hip) so that the three instantiation sets compile in parallel.
+// a camera rig").  Included by one unit per interpolation (lrp_camgain.hip; lrp_camgain_unit.hip twice,
+// units.list) so that the three instantiation sets compile in parallel.
 //
 // Per output pixel: compose_ss_pixel (lrp_compose_pixel.h) as compose_cam_kernel instantiates it (CameraSources,
 // IdealTarget<OutLens>), with CameraGainHook below as the per-sample hook: right after sampling, the first min(C, 3) channels
@@ -59,4 +59,6 @@ template <int Interp> hipError_t launch_compose_cameras_gain_interp(CameraGainPa
   return launch_compose_tiles(camgain_kernel_of<Interp>(out_lens), G, G.cam, stream);
 }
 
+// ... as a bilinear / bicubic unit of units.list compiles it: defined and instantiated by lrp_camgain_unit.hip, declared only for the launcher.
+template <int Interp> hipError_t launch_compose_cameras_gain_unit(const CameraGainParams &G, int out_lens, hipStream_t stream);
 } // namespace lrp

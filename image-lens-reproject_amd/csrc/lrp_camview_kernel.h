@@ -1,7 +1,7 @@
 // lrp_camview_kernel.h — the camera-view kernel (include/lrp.h "calibrated camera as the target"): frames
 // of calibrated cameras composed into the frame of another calibrated camera — a new camera matrix, camera-to-camera remapping,
-// re-distortion — with n x n sub-samples per pixel, one launch.  Included by one .hip unit per interpolation (lrp_camview.hip,
-// lrp_camview_bl.hip, lrp_camview_bc.hip) so that the three instantiation sets compile in parallel.
+// re-distortion — with n x n sub-samples per pixel, one launch.  Included by one unit per interpolation (lrp_camview.hip;
+// lrp_camview_unit.hip twice, units.list) so that the three instantiation sets compile in parallel.
 //
 // Per output pixel: compose_ss_pixel (lrp_compose_pixel.h) with CameraSources (lrp_camera_kernel.h) and, in place of the target
 // of an ideal lens, CameraTarget<TargetModel> below: camera_unproject (lrp_camera_inverse.h), the Newton inverse of the target's
@@ -52,4 +52,6 @@ template <int Interp> hipError_t launch_camera_view_interp(CameraViewParams P, h
   return launch_compose_tiles(fn, P, P, stream);
 }
 
+// ... as a bilinear / bicubic unit of units.list compiles it: defined and instantiated by lrp_camview_unit.hip, declared only for the launcher.
+template <int Interp> hipError_t launch_camera_view_unit(const CameraViewParams &P, hipStream_t stream);
 } // namespace lrp

@@ -1,8 +1,8 @@
 // lrp_capi.cpp — the C ABI declared in include/lrp.h: argument validation in the
 // reference's dispatch order, kernel-argument construction, device buffers,
 // streams and the batch context.  Host code only; the kernels live in the
-// lrp_kernels_*.hip / lrp_tile_*.hip / lrp_eqs_*.hip / lrp_stg_*.hip (reprojection), lrp_tables.hip, lrp_geo_lists.hip,
-// lrp_coverage.hip (coverage planes), lrp_compose*.hip (compose), lrp_camera*.hip (compose, calibrated cameras), lrp_camview*.hip (a calibrated camera as the target), lrp_packed*.hip (packed pixels), lrp_lanczos*.hip (the Lanczos-3 sampler), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units.
+// lrp_kernels_*.hip / lrp_tile_*.hip / lrp_{pixel,tile,win}_unit.hip (reprojection), lrp_tables.hip, lrp_geo_lists.hip,
+// lrp_coverage.hip (coverage planes), lrp_compose*.hip (compose), lrp_camera*.hip (compose, calibrated cameras), lrp_camview*.hip (a calibrated camera as the target), lrp_packed*.hip (packed pixels), lrp_lanczos*.hip (the Lanczos-3 sampler), lrp_pixel_kernels.hip and lrp_aux_kernels.hip translation units; units.list names every object and what it is compiled from.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

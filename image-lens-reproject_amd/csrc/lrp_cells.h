@@ -41,9 +41,9 @@ constexpr bool geo_big_cell(int out_lens, int in_mode) {
 
 // ---- which unit compiles a cell -------------------------------------------------------------------
 // The cells with an extension lens are instantiated by units of their own, next to the units of the reference's lenses: a
-// unit's launcher takes its set as a template argument and its tables are null elsewhere.  kStgCells (lrp_stg_*.hip): every
-// cell with a stereographic lens, the two it shares with the equisolid lens included; kEqsCells (lrp_eqs_*.hip): the other
-// cells with an equisolid lens.
+// unit's launcher takes its set as a template argument and its tables are null elsewhere.  kStgCells (lrp_stg_*.o): every
+// cell with a stereographic lens, the two it shares with the equisolid lens included; kEqsCells (lrp_eqs_*.o): the other
+// cells with an equisolid lens.  Those objects are lines of units.list: lrp_{pixel,tile,win}_unit.hip with the set as a define.
 enum CellSet : int { kStdCells = 0, kEqsCells = 1, kStgCells = 2 };
 constexpr CellSet cell_set_of(int out_lens, int in_mode) {
   return has_stereographic(out_lens, in_mode) ? kStgCells : has_equisolid(out_lens, in_mode) ? kEqsCells : kStdCells;

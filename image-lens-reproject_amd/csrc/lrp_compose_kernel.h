@@ -1,5 +1,5 @@
 // lrp_compose_kernel.h — the compose kernel (include/lrp.h "compose"): several source images into one
-// output, one launch.  Included by one .hip unit per interpolation (lrp_compose.hip, lrp_compose_bl.hip, lrp_compose_bc.hip)
+// output, one launch.  Included by one unit per interpolation (lrp_compose.hip; lrp_compose_unit.hip twice, units.list)
 // so that the three instantiation sets compile in parallel.
 //
 // Per output pixel: the target ray once; then, source by source, the rotation, ray_to_source and the coverage test of
@@ -191,4 +191,6 @@ template <int Interp> hipError_t launch_compose_interp(ComposeParams P, int out_
   return launch_compose_tiles(compose_cell_kernel<Interp>(out_lens, in_mode), P, P, stream);
 }
 
+// ... as a bilinear / bicubic unit of units.list compiles it: defined and instantiated by lrp_compose_unit.hip, declared only for the launcher.
+template <int Interp> hipError_t launch_compose_unit(const ComposeParams &P, int out_lens, int in_mode, hipStream_t stream);
 } // namespace lrp

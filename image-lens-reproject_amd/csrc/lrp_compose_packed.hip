@@ -1,16 +1,13 @@
 // lrp_compose_packed.hip — several packed sources composed into one packed output by one launch (include/lrp.h "compose, packed
 // pixels"): the launcher lrp_capi.cpp calls, and the nearest-neighbour instantiations of
-// compose_packed_kernel (lrp_compose_packed_kernel.h).  The bilinear ones are lrp_compose_packed_bl.hip, the bicubic ones
-// lrp_compose_packed_bc.hip (8-bit sources) and lrp_compose_packed_bc_f16.hip (half sources).
+// compose_packed_kernel (lrp_compose_packed_kernel.h).  The bilinear ones and, one source format each, the bicubic ones
+// are units of lrp_compose_packed_unit.hip (units.list).
 #include <hip/hip_runtime.h>
 
 #include "lrp_compose_packed_kernel.h"
 
 namespace lrp {
 
-hipError_t launch_compose_packed_bilinear(const ComposePackedParams &P, int in_format, int out_lens, int in_mode, hipStream_t stream);
-hipError_t launch_compose_packed_bicubic_u8(const ComposePackedParams &P, int out_lens, int in_mode, hipStream_t stream);
-hipError_t launch_compose_packed_bicubic_f16(const ComposePackedParams &P, int out_lens, int in_mode, hipStream_t stream);
 hipError_t pixel_tables_device(int device, hipStream_t stream, const float **decode, const float **threshold); // lrp_pixel_kernels.hip
 
 // P: what lrp_capi.cpp states (lrp_compose_packed.h); the rest is derived here.  in_format: kPackedF16 / kPackedU8.
@@ -32,9 +29,10 @@ hipError_t launch_compose_packed(ComposePackedParams P, int in_format, int out_l
   P.tiles_x = (P.out_w + kComposeTileW - 1) / kComposeTileW;
   P.tiles_y = (P.out_h + kComposeTileH - 1) / kComposeTileH;
   if (interpolation == 0) return launch_compose_packed_interp<0>(P, in_format, out_lens, in_mode, stream);
-  if (interpolation == 1) return launch_compose_packed_bilinear(P, in_format, out_lens, in_mode, stream);
+  if (interpolation == 1)
+    return in_format == kPackedU8 ? launch_compose_packed_unit<1, kPackedU8>(P, out_lens, in_mode, stream) : launch_compose_packed_unit<1, kPackedF16>(P, out_lens, in_mode, stream);
   if (interpolation == 2)
-    return in_format == kPackedU8 ? launch_compose_packed_bicubic_u8(P, out_lens, in_mode, stream) : launch_compose_packed_bicubic_f16(P, out_lens, in_mode, stream);
+    return in_format == kPackedU8 ? launch_compose_packed_unit<2, kPackedU8>(P, out_lens, in_mode, stream) : launch_compose_packed_unit<2, kPackedF16>(P, out_lens, in_mode, stream);
   return hipErrorInvalidValue;
 }
 

@@ -1,7 +1,7 @@
 // lrp_compose_packed_kernel.h — the packed compose kernel (include/lrp.h "compose, packed pixels"): several
 // sources of 8-bit or binary16 samples composed into one output of 8-bit, binary16 or float samples by one launch.  Included by
-// one .hip unit per interpolation (lrp_compose_packed.hip, lrp_compose_packed_bl.hip, lrp_compose_packed_bc.hip) so that the
-// three instantiation sets compile in parallel.
+// one unit per interpolation (lrp_compose_packed.hip; lrp_compose_packed_unit.hip, units.list) and, for the bicubic sampler,
+// one per source format, so that the instantiation sets compile in parallel.
 //
 // The bytes are those of lrp_decode_pixels_device per source -> lrp_compose_device -> lrp_encode_pixels_device with float32
 // staging images of C channels in between.  It is compose_kernel's body (lrp_compose_kernel.h) between packed_kernel's two ends
@@ -151,7 +151,7 @@ template <int Interp, int CH, int Fmt> ComposePackedKernelFn compose_packed_cell
   return table[out_lens * kInModes + in_mode];
 }
 
-// One source format's kernels: the unit of the split of the bicubic instantiations (lrp_compose_packed_bc*.hip).
+// One source format's kernels: the unit of the split of the bicubic instantiations (units.list, lrp_compose_packed_bc*.o).
 template <int Interp, int Fmt> hipError_t launch_compose_packed_fmt(const ComposePackedParams &P, int out_lens, int in_mode, hipStream_t stream) {
   if (P.tiles_x <= 0 || P.tiles_y <= 0) return hipSuccess;
   const ComposePackedKernelFn fn =
@@ -168,4 +168,7 @@ template <int Interp> hipError_t launch_compose_packed_interp(const ComposePacke
   return launch_compose_packed_fmt<Interp, kPackedF16>(P, out_lens, in_mode, stream);
 }
 
+// launch_compose_packed_fmt as a bilinear / bicubic unit of units.list compiles it: defined and instantiated by
+// lrp_compose_packed_unit.hip, declared only for the launcher.
+template <int Interp, int Fmt> hipError_t launch_compose_packed_unit(const ComposePackedParams &P, int out_lens, int in_mode, hipStream_t stream);
 } // namespace lrp

@@ -1,6 +1,6 @@
 // lrp_compose_ss_kernel.h — the supersampled compose kernel (include/lrp.h "compose, supersampled"):
-// several source images into one output with n x n sub-samples per pixel, one launch.  Included by one .hip unit per
-// interpolation (lrp_compose_ss.hip, lrp_compose_ss_bl.hip, lrp_compose_ss_bc.hip) so that the three instantiation sets
+// several source images into one output with n x n sub-samples per pixel, one launch.  Included by one unit per
+// interpolation (lrp_compose_ss.hip; lrp_compose_ss_unit.hip twice, units.list) so that the three instantiation sets
 // compile in parallel.
 //
 // Per output pixel: compose_ss_pixel (lrp_compose_pixel.h), the supersampled body, with the sources and the target of ideal
@@ -50,4 +50,6 @@ template <int Interp> hipError_t launch_compose_ss_interp(ComposeSsParams P, int
   return launch_compose_tiles(compose_ss_cell_kernel<Interp>(out_lens, in_mode), P, P, stream);
 }
 
+// ... as a bilinear / bicubic unit of units.list compiles it: defined and instantiated by lrp_compose_ss_unit.hip, declared only for the launcher.
+template <int Interp> hipError_t launch_compose_ss_unit(const ComposeSsParams &P, int out_lens, int in_mode, hipStream_t stream);
 } // namespace lrp

@@ -1,6 +1,6 @@
 // lrp_kernel_impl.h — the reprojection kernel template and its launch table.
 // Included by one .hip translation unit per interpolation mode so the three
-// instantiation sets compile in parallel.
+// instantiation sets compile in parallel, and by lrp_pixel_unit.hip per extension lens.
 //
 // Mapping (gfx950): a 256-thread workgroup owns a TILE_W x TILE_H block of
 // output pixels; each 64-lane wavefront owns two contiguous 32-pixel row
@@ -87,5 +87,9 @@ hipError_t launch_interp(KParams P, int out_lens, int in_mode, hipStream_t strea
   hipLaunchKernelGGL(fn, grid, block, 0, stream, P);
   return hipGetLastError();
 }
+
+// launch_interp for the cells of an extension lens, as one unit of units.list compiles it: defined and instantiated by
+// lrp_pixel_unit.hip; the dispatchers (lrp_kernels_{nn,bl,bc}.hip) see this declaration only.
+template <int Interp, CellSet Set> hipError_t launch_pixel_unit(const KParams &P, int out_lens, int in_mode, hipStream_t stream);
 
 } // namespace lrp

@@ -3,11 +3,9 @@
 #include "lrp_kernel_impl.h"
 
 namespace lrp {
-hipError_t launch_bicubic_eqs(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_eqs_pixel.hip
-hipError_t launch_bicubic_stg(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_stg_pixel.hip
 hipError_t launch_bicubic(const KParams &P, int out_lens, int in_mode, hipStream_t stream) {
-  if (launch_cell_set(P, out_lens, in_mode) == kEqsCells) return launch_bicubic_eqs(P, out_lens, in_mode, stream);
-  if (launch_cell_set(P, out_lens, in_mode) == kStgCells) return launch_bicubic_stg(P, out_lens, in_mode, stream);
+  if (launch_cell_set(P, out_lens, in_mode) == kEqsCells) return launch_pixel_unit<2, kEqsCells>(P, out_lens, in_mode, stream);
+  if (launch_cell_set(P, out_lens, in_mode) == kStgCells) return launch_pixel_unit<2, kStgCells>(P, out_lens, in_mode, stream);
   return launch_interp<2>(P, out_lens, in_mode, stream);
 }
 } // namespace lrp

@@ -1,14 +1,12 @@
 // lrp_packed.hip — packed pixels reprojected by one launch (include/lrp.h "packed pixels"): the launcher
 // lrp_capi.cpp calls, and the nearest-neighbour instantiations of packed_kernel (lrp_packed_kernel.h).  The bilinear and
-// bicubic ones are lrp_packed_bl.hip and lrp_packed_bc.hip.
+// bicubic ones are units of lrp_packed_unit.hip (units.list).
 #include <hip/hip_runtime.h>
 
 #include "lrp_packed_kernel.h"
 
 namespace lrp {
 
-hipError_t launch_packed_bilinear(const PackedParams &P, int in_format, int out_lens, int in_mode, hipStream_t stream);
-hipError_t launch_packed_bicubic(const PackedParams &P, int in_format, int out_lens, int in_mode, hipStream_t stream);
 hipError_t pixel_tables_device(int device, hipStream_t stream, const float **decode, const float **threshold); // lrp_pixel_kernels.hip
 
 // P: what lrp_capi.cpp states (lrp_packed.h); the rest is derived here.  in_format: kPackedF16 / kPackedU8.
@@ -30,8 +28,8 @@ hipError_t launch_packed(PackedParams P, int in_format, int out_lens, int in_mod
   P.tiles_x = (P.out_w + kPackedTileW - 1) / kPackedTileW;
   P.tiles_y = (P.out_h + kPackedTileH - 1) / kPackedTileH;
   if (interpolation == 0) return launch_packed_interp<0>(P, in_format, out_lens, in_mode, stream);
-  if (interpolation == 1) return launch_packed_bilinear(P, in_format, out_lens, in_mode, stream);
-  if (interpolation == 2) return launch_packed_bicubic(P, in_format, out_lens, in_mode, stream);
+  if (interpolation == 1) return launch_packed_unit<1>(P, in_format, out_lens, in_mode, stream);
+  if (interpolation == 2) return launch_packed_unit<2>(P, in_format, out_lens, in_mode, stream);
   return hipErrorInvalidValue;
 }
 

@@ -1,6 +1,6 @@
 // lrp_packed_kernel.h — the packed-pixel kernel (include/lrp.h "packed pixels"): a source of 8-bit or
-// binary16 samples reprojected into an output of 8-bit, binary16 or float samples by one launch.  Included by one .hip unit
-// per interpolation (lrp_packed.hip, lrp_packed_bl.hip, lrp_packed_bc.hip) so that the three instantiation sets compile in
+// binary16 samples reprojected into an output of 8-bit, binary16 or float samples by one launch.  Included by one unit
+// per interpolation (lrp_packed.hip; lrp_packed_unit.hip twice, units.list) so that the three instantiation sets compile in
 // parallel.
 //
 // The bytes are those of lrp_decode_pixels_device -> lrp_reproject_device -> lrp_encode_pixels_device with float32 staging
@@ -237,4 +237,6 @@ template <int Interp> hipError_t launch_packed_interp(const PackedParams &P, int
   return hipGetLastError();
 }
 
+// ... as a bilinear / bicubic unit of units.list compiles it: defined and instantiated by lrp_packed_unit.hip, declared only for the launcher.
+template <int Interp> hipError_t launch_packed_unit(const PackedParams &P, int in_format, int out_lens, int in_mode, hipStream_t stream);
 } // namespace lrp

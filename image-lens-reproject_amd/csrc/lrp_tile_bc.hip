@@ -2,11 +2,9 @@
 #include "lrp_kernel_v2.h"
 
 namespace lrp {
-hipError_t launch_tile_bicubic_eqs(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_eqs_tile_bc.hip
-hipError_t launch_tile_bicubic_stg(const KParams &P, int out_lens, int in_mode, hipStream_t stream); // lrp_stg_tile_bc.hip
 hipError_t launch_tile_bicubic(const KParams &P, int out_lens, int in_mode, hipStream_t stream) {
-  if (launch_cell_set(P, out_lens, in_mode) == kEqsCells) return launch_tile_bicubic_eqs(P, out_lens, in_mode, stream);
-  if (launch_cell_set(P, out_lens, in_mode) == kStgCells) return launch_tile_bicubic_stg(P, out_lens, in_mode, stream);
+  if (launch_cell_set(P, out_lens, in_mode) == kEqsCells) return launch_tile_unit<2, kEqsCells>(P, out_lens, in_mode, stream);
+  if (launch_cell_set(P, out_lens, in_mode) == kStgCells) return launch_tile_unit<2, kStgCells>(P, out_lens, in_mode, stream);
   return launch_tile_interp<2>(P, out_lens, in_mode, stream);
 }
 } // namespace lrp

@@ -342,4 +342,8 @@ template <int Interp, CellSet Set = kStdCells> hipError_t launch_tile_interp(KPa
   return hipGetLastError();
 }
 
+// launch_tile_interp for the cells of an extension lens, as one unit of units.list compiles it: defined and instantiated
+// by lrp_tile_unit.hip; the dispatchers (lrp_tile_{nn,bl,bc}.hip) see this declaration only.
+template <int Interp, CellSet Set> hipError_t launch_tile_unit(const KParams &P, int out_lens, int in_mode, hipStream_t stream);
+
 } // namespace lrp

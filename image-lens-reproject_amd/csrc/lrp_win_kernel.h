@@ -1856,4 +1856,10 @@ inline hipError_t launch_win_bicubic_impl(KParams P, int out_lens, int in_mode, 
   return hipGetLastError();
 }
 
+// launch_win_bicubic_impl as one unit of units.list compiles it.  lrp_win_unit.hip defines this and instantiates it once per
+// manifest line; the dispatcher (lrp_tile_win.hip) names an instantiation by its parameters and sees this declaration only,
+// so its object references the unit's and holds none of its kernels.
+template <int QMode, int CH, bool GeoRead = false, bool SS = false, CellSet Set = kStdCells>
+hipError_t launch_win_unit(const KParams &P, int out_lens, int in_mode, hipStream_t stream);
+
 } // namespace lrp

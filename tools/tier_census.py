@@ -5,7 +5,7 @@ mapping — the census DESIGN.md sections 4.1 and 5 quote.  Needs a diagnostic b
     tools/ablate.sh ts:-DLRP_TIER_STATS          # -> tools/_ablate/ts/liblrp_hip.so
     python3 tools/tier_census.py tools/_ablate/ts/liblrp_hip.so        (on an MI355X box)
 
-The counters live in the plain-block RGBA unit (lrp_tile_win.hip), so the mirror modes are switched off for the run; the
+The counters live in the plain-block RGBA unit (lrp_tile_win.o of csrc/units.list: lrp_tile_win.hip), so the mirror modes are switched off for the run; the
 tier of a block does not depend on the mode.  The cubemap faces (8192^2 -> 2048^2) are rendered as RGBA stand-ins."""
 import ctypes
 import importlib

@@ -2,7 +2,7 @@
 """Where a single launch of the window kernel loses time: start / end of every wavefront (100 MHz wall clock) and the
 hardware slot it ran in, from a diagnostic build that records them:
 
-    tools/ablate_units.sh stamps lrp_tile_wing.hip -DLRP_WAVE_STAMPS      # -> tools/_ablate/stamps/liblrp_hip.so
+    tools/ablate_units.sh stamps lrp_tile_wing -DLRP_WAVE_STAMPS    # (a unit of csrc/units.list) -> tools/_ablate/stamps/liblrp_hip.so
     python3 tools/wave_timeline.py tools/_ablate/stamps/liblrp_hip.so [in_lens out_lens]      (on an MI355X box)
 
 Prints the span of the launch, the lifetimes of its wavefronts, how full the wave slots were over the launch, the ramp
